@@ -26,6 +26,12 @@ Launched as `python bench.py --gpus N --steps K --warmup W`.  For N > 1 outside 
 relays rank 0's line; under torchrun every rank checks WORLD_SIZE == --gpus.  One rank per GPU, RCCL all-reduce
 of the counters; OFDM_DIST_BACKEND=gloo reduces host copies instead (several ranks sharing one GPU: the tests'
 world-2 run on a 1-GPU box).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what the headline figure does
+not need: the reference's own timing on the host (`cpu_baseline`, about --cpu-seconds before the GPU is touched;
+--no-cpu-baseline leaves it out again).  `--dump-outputs DIR` writes what the last timed step returned to its caller
+as DIR/<name>.npy (dump_outputs): with the same arguments the inputs, and so these files, are the same from run to
+run, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -359,6 +365,37 @@ def cpu_baseline_fft(ref, seconds: float, share: dict | None) -> dict:
             "single_core": single}
 
 
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_FFT_ROWS = 1 << 15            # fft64: sampled transforms per buffer (2 buffers x 2^15 x 64 x 8 B = 32 MiB)
+DUMP_SEED = 0x80211A
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """--dump-outputs: every array as <out_dir>/<name>.npy, float32 or float64 (complex arrays as a trailing
+    (re, im) axis of their component type), at most DUMP_MAX_BYTES in all."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if np.iscomplexobj(a):
+            a = a.view(a.real.dtype).reshape(*a.shape, 2)
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would write more than {DUMP_MAX_BYTES} bytes")
+        np.save(d / f"{name}.npy", a)
+
+
+def sample_rows(n: int, k: int = DUMP_FFT_ROWS) -> np.ndarray:
+    """The fixed sample of a large output's rows that --dump-outputs keeps: k of n row indices, sorted, drawn
+    without replacement from a generator seeded with DUMP_SEED (every row when n <= k)."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
 def plan_chunks(first: int, frames: int, n_chunks: int = 0) -> list[tuple[int, int]]:
     """Equal chunks (no small tail launch) of at most MAX_CHUNK_FRAMES frames, and at least PIPE_CHUNKS of
     them (each >= MIN_PIPE_FRAMES) so that the Tx of chunk k+1 can be built under the receiver of chunk k
@@ -476,6 +513,12 @@ def run_fft64(args, cpu, torch, dist, pkg, abi, codeobj, rank, world, dev, distr
     cert, why = certify_pmc(pmc, "fft64_lds_kernel", lib_id)
     tpu = cert.get("hbm_bytes_per_unit")
     value = 2.0 * n * world * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        # the step's two results: the spectra (y, of the batch the step started from) and the batch itself after
+        # the inverse transform (x); rank 0's buffers, a fixed sample of their rows
+        rows = torch.from_numpy(sample_rows(n)).to(x.device)
+        dump_outputs(args.dump_outputs, {"rows": rows.cpu().numpy(), "fft": y[rows].cpu().numpy(),
+                                         "ifft": x[rows].cpu().numpy()})
     if rank == 0:
         line = {
             "metric": "OFDM symbols/sec (whole node) over BER-vs-SNR sweep; achieved HBM GB/s vs peak",
@@ -582,7 +625,11 @@ def main():
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--symbols", type=int, default=0,
                     help="override data symbols per SNR point (per GPU for weak workloads, total for strong)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the reference on the host first (cpu_baseline in the line); a plain run does not")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the host timing out")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--chunks", type=int, default=0, help="Tx/receiver chunks per step (0: plan_chunks)")
     ap.add_argument("--pipeline", choices=("auto", "fused", "streams"), default="auto",
@@ -595,15 +642,17 @@ def main():
     args.warmup = dflt[1] if args.warmup is None else args.warmup
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "RANK" not in os.environ and args.gpus > 1:
         # one rank per GPU: this process only launches them (nothing here touches the GPU)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     check_world(args)
 
-    # host-side reference timing first, before anything touches the GPU (worker processes are spawned).
+    # --full: host-side reference timing first, before anything touches the GPU (worker processes are spawned).
     # Under torchrun rank 0 (local rank 0 of the one node) times it before forming the process group; the
     # other ranks wait at the rendezvous, so every N-GPU line carries the CPU figure of the same run
-    cpu = cpu_baseline(args.workload, args.cpu_seconds) if wants_cpu_baseline(args) else None
+    cpu = cpu_baseline(args.workload, args.cpu_seconds) if args.full and wants_cpu_baseline(args) else None
 
     import torch
     import torch.distributed as dist
@@ -697,6 +746,11 @@ def main():
     units_per_launch = frames * dpf * n_snr * args.steps / max(rx_n, 1)  # this rank's units per receiver launch
     bytes_per_unit = FRAME_CAPTURE_SAMPLES[args.workload] * 8 / dpf if frame_mode else BYTES_PER_SYMBOL_SNR
     res = pkg.SweepResult(SNR_GRID, c)
+    if rank == 0 and args.dump_outputs:
+        # what the last step handed back: the job's counters (one row of int64 sums per SNR point, exact in
+        # float64) and the curves read from them
+        dump_outputs(args.dump_outputs, {"snr_db": SNR_GRID, "counters": c, "ber": res.ber,
+                                         "evm_pre_db": res.evm_pre_db})
     pmc = load_pmc(args.workload)
     # the receiver kernel this workload launches (ofdm_symbol.hip launch_rx): real-noise AWGN sweeps and
     # real-noise LS Rayleigh sweeps run the packed receiver (ofdm_rxpack.hip), the others the {E, D0, D1}

@@ -29,7 +29,9 @@ def build_oracle() -> Path:
 
 def build_ref() -> Path | None:
     """Compile the reference (only where its source exists: this container, not the GPU box)."""
-    if not REF_SRC.exists():
+    # os.path.exists, not Path.exists: a reference tree under a directory this user may not enter is "not here"
+    # (Path.exists raises PermissionError there)
+    if not os.path.exists(REF_SRC):
         return REF_SO if REF_SO.exists() else None
     subprocess.run(["make", "-s", "ref", f"REF_SRC={REF_SRC}"], cwd=ORACLE_DIR, check=True)
     return REF_SO

@@ -545,3 +545,109 @@ def test_frame8_classified_cap():
     assert 0.58 < m["sync"]["cap_frac"] < 0.71 and 0.55 < m["cap_frac"] < 0.75
     assert abs(m["sync"]["class_check_per_item"]["mul_f32"]["model"] /
                m["sync"]["class_check_per_item"]["mul_f32"]["measured"] - 1) < 0.1
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: every array lands as <name>.npy in float32 or float64 (int64 counters exactly, complex64 as
+    float32 (re, im) pairs), the row sample of a large output is fixed, and more than 64 MB in all is refused."""
+    b = _bench()
+    c = np.arange(32, dtype=np.int64).reshape(2, 16) + (1 << 40)
+    z = (np.arange(6, dtype=np.float32).reshape(3, 2) * (1 + 2j)).astype(np.complex64)
+    b.dump_outputs(tmp_path / "d", {"counters": c, "fft": z, "ber": np.array([0.5, 0.25])})
+    got = {p.name: np.load(p, allow_pickle=False) for p in (tmp_path / "d").iterdir()}
+    assert sorted(got) == ["ber.npy", "counters.npy", "fft.npy"]
+    assert got["counters.npy"].dtype == np.float64 and np.array_equal(got["counters.npy"].astype(np.int64), c)
+    assert got["fft.npy"].dtype == np.float32 and got["fft.npy"].shape == (3, 2, 2)
+    assert np.array_equal(got["fft.npy"][..., 0], z.real) and np.array_equal(got["fft.npy"][..., 1], z.imag)
+    assert got["ber.npy"].dtype == np.float64
+    rows = b.sample_rows(1 << 24)
+    assert len(rows) == b.DUMP_FFT_ROWS == len(np.unique(rows)) and np.array_equal(rows, np.sort(rows))
+    assert 0 <= rows[0] and rows[-1] < 1 << 24 and np.array_equal(rows, b.sample_rows(1 << 24))
+    assert np.array_equal(b.sample_rows(100), np.arange(100))
+    assert 2 * b.DUMP_FFT_ROWS * 64 * 8 + 8 * b.DUMP_FFT_ROWS <= b.DUMP_MAX_BYTES       # fft64's three files
+    with pytest.raises(SystemExit):
+        b.dump_outputs(tmp_path / "big", {"x": np.zeros(b.DUMP_MAX_BYTES // 8 + 1)})
+
+
+def test_plain_run_does_not_time_the_reference(monkeypatch):
+    """A plain run does only what its headline figure needs: the host timing of the reference (cpu_baseline) runs
+    only with --full (and not with --no-cpu-baseline).  main() is stopped where it would first touch the GPU."""
+    b = _bench()
+    calls = []
+
+    class Stop(Exception):
+        pass
+
+    def stop():
+        raise Stop
+
+    monkeypatch.setattr(b, "cpu_baseline", lambda w, s: calls.append((w, s)))
+    monkeypatch.setattr(b.ofdm_pkg, "load", stop)
+    monkeypatch.delenv("RANK", raising=False)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    for argv, want in ((["--gpus", "1", "--steps", "3", "--warmup", "1"], []),
+                       (["--full", "--workload", "c2", "--cpu-seconds", "0.5"], [("c2", 0.5)]),
+                       (["--full", "--no-cpu-baseline"], [])):
+        calls.clear()
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        with pytest.raises(Stop):
+            b.main()
+        assert calls == want, argv
+
+
+def _run_bench(argv):
+    import os
+    import subprocess
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), *argv], capture_output=True, text=True, timeout=240,
+                       env=dict(os.environ, PYTHONUNBUFFERED="1"), cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = r.stdout.strip().splitlines()
+    assert len(out) == 1, out
+    return json.loads(out[0])
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_steps_counters(engine, pkg, tmp_path):
+    """`bench.py --dump-outputs DIR` (c3, a plain run): the files hold the counters of the last timed step -- those
+    of one ofdm_symbol_sweep over the same frames, exactly -- and the curves of the line; the line has ms_per_step
+    for the --steps asked and, without --full, no cpu_baseline."""
+    b = _bench()
+    symbols = 200_000
+    line = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--symbols", str(symbols),
+                       "--dump-outputs", str(tmp_path / "out")])
+    assert line["steps"] == 3 and line["warmup"] == 1 and "cpu_baseline" not in line
+    assert line["value"] == pytest.approx(symbols * 16 * 3 / (line["ms_per_step"] * 3 / 1e3))
+    got = {p.stem: np.load(p, allow_pickle=False) for p in (tmp_path / "out").iterdir()}
+    assert sorted(got) == ["ber", "counters", "evm_pre_db", "snr_db"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    want = engine.symbol_sweep(pkg.make_cfg(**b.WORKLOADS["c3"][1]), b.SNR_GRID, symbols // 2)
+    assert np.array_equal(got["counters"].astype(np.int64), want)
+    assert np.array_equal(got["snr_db"], b.SNR_GRID)
+    assert got["ber"].tolist() == line["results"]["ber"] and got["evm_pre_db"].tolist() == line["results"]["evm_pre_db"]
+
+
+@pytest.mark.gpu
+def test_bench_dumps_a_fixed_sample_of_the_fft_buffers(engine, tmp_path):
+    """`bench.py --workload fft64 --dump-outputs DIR`: after 1 + 2 steps the spectra buffer holds fft() of the seeded
+    batch (two fft + ifft round trips roll it by 64 = 0 samples) and the batch buffer that batch rolled by 32; the
+    files hold the fixed sample of 2^15 of their 2^16 rows, as float32 (re, im) pairs."""
+    import torch
+    b = _bench()
+    n = 1 << 16
+    _run_bench(["--gpus", "1", "--workload", "fft64", "--symbols", str(n), "--steps", "2", "--warmup", "1",
+                "--dump-outputs", str(tmp_path / "out")])
+    got = {p.stem: np.load(p, allow_pickle=False) for p in (tmp_path / "out").iterdir()}
+    assert sorted(got) == ["fft", "ifft", "rows"]
+    rows = got["rows"].astype(np.int64)
+    assert np.array_equal(rows, b.sample_rows(n)) and len(rows) == b.DUMP_FFT_ROWS
+    assert got["fft"].dtype == got["ifft"].dtype == np.float32
+    assert got["fft"].shape == got["ifft"].shape == (len(rows), 64, 2)
+    g = torch.Generator(device="cuda:0").manual_seed(0x80211A)
+    x0 = torch.randn((n, 64), dtype=torch.complex64, device="cuda:0", generator=g)
+    want_y = engine.fft64(x0)[torch.from_numpy(rows).cuda()].cpu().numpy()
+    want_x = x0.roll(32, dims=1)[torch.from_numpy(rows).cuda()].cpu().numpy()
+    y = got["fft"][..., 0] + 1j * got["fft"][..., 1]
+    x = got["ifft"][..., 0] + 1j * got["ifft"][..., 1]
+    # three f32 transforms of 64 points apart: a few ulp of the largest bin (the bench's own round-trip bound is 1e-5)
+    assert np.max(np.abs(y - want_y)) <= 1e-5 * np.max(np.abs(want_y))
+    assert np.max(np.abs(x - want_x)) <= 1e-5 * np.max(np.abs(want_x))

@@ -1,6 +1,7 @@
 """Host-side checks that need no GPU: the C-ABI library loads and exports every symbol its header
 declares, the ctypes structs match the header, the file writer keeps the reference format."""
 import json
+import os
 import re
 import subprocess
 import sys
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from oracle.orc import REF_SRC
 
 
 def header_functions():
@@ -120,19 +122,58 @@ def test_write_reference_outputs_refuses_missing_dir(pkg, tmp_path):
         pkg.write_reference_outputs(tmp_path / "nope", [1], [1], [1], [1])
 
 
-@pytest.mark.skipif(not (ROOT.parent / "reference" / "scripts" / "OFDM_Plotting.py").exists(),
-                    reason="reference scripts only exist in the build container")
+# The reference tree (its scripts/ and data/), where it is present: next to the source the oracle's `ref`
+# recipe compiles (OFDM_REF_SRC).  os.path.exists: a tree this user may not enter counts as absent.  The tests
+# below check the project's files on their own and, where the tree is here, also run its scripts unchanged.
+REF_TREE = REF_SRC.parent.parent
+REF_SCRIPTS = REF_TREE / "scripts"
+HAVE_REF_SCRIPTS = os.path.exists(REF_SCRIPTS / "compare_double.py") and os.path.exists(REF_SCRIPTS / "OFDM_Plotting.py")
+GPU_KAT_FILE = GOLDEN / "gpu_kat_Code_Output.txt"
+MATLAB_FILE = GOLDEN / "Matlab_Output.txt"         # the reference's data/Matlab_Output.txt, byte for byte
+
+
+def _script_numbers(text):
+    """A result file as the reference's scripts read it (compare_double.py / OFDM_Plotting.py read_double_file):
+    newlines to blanks, split on white space, every word a float; the plotting script maps INF / inf words by sign
+    and NaN / #J / #IND words to -40."""
+    out = []
+    for w in text.replace("\n", " ").split():
+        if "INF" in w or "inf" in w:
+            out.append(float("-inf") if "-" in w else float("inf"))
+        elif "NaN" in w or "#J" in w or "#IND" in w:
+            out.append(-40.0)
+        else:
+            out.append(float(w))
+    return out
+
+
 def test_reference_plotting_script_reads_our_files(pkg, tmp_path):
-    """scripts/OFDM_Plotting.py must drop in unchanged.  It resolves data/ and results/ relative to
-    its own location, so it is run from a scratch copy of its directory layout."""
-    pytest.importorskip("matplotlib")
-    import shutil
+    """scripts/OFDM_Plotting.py must drop in unchanged.  The four files write_reference_outputs leaves in data/ parse
+    by the script's own reading rule into the 35 values written, in the layout of the reference's own result files
+    (tests/golden/reference_data.json: tab-separated words, one line).  Where the reference tree is present
+    the script itself is run as well: it resolves data/ and results/ relative to its own location, so it runs from a
+    scratch copy of its directory layout."""
     base = tmp_path / "ref"
     (base / "scripts").mkdir(parents=True)
     (base / "data").mkdir()
-    shutil.copy(ROOT.parent / "reference" / "scripts" / "OFDM_Plotting.py", base / "scripts")
     snr = np.arange(6, 41)
-    pkg.write_reference_outputs(base / "data", snr, -snr - 1.3, np.full(35, -np.inf), np.where(snr < 10, 1e-2, 0))
+    evm, evm_agc, ber = -snr - 1.3, np.full(35, -np.inf), np.where(snr < 10, 1e-2, 0)
+    pkg.write_reference_outputs(base / "data", snr, evm, evm_agc, ber)
+    theirs = json.loads((GOLDEN / "reference_data.json").read_text())
+    assert sorted(p.name for p in (base / "data").iterdir()) == sorted(theirs)
+    for name, want in (("Output_SNR.txt", snr), ("Output_EVM_AGC.txt", evm), ("Output_EVM_AGC_DB.txt", evm_agc),
+                       ("Output_BER.txt", ber)):
+        text = (base / "data" / name).read_text()
+        got = _script_numbers(text)
+        assert len(got) == 35 == len(_script_numbers(theirs[name])), name
+        # %.2e as the reference writes it: three significant digits
+        assert np.array_equal(np.isinf(got), np.isinf(want)) and np.allclose(got, want, rtol=5.1e-3, atol=0), name
+        assert text.count("\n") == theirs[name].count("\n") and text.count("\t") == theirs[name].count("\t"), name
+    import importlib.util
+    if not HAVE_REF_SCRIPTS or importlib.util.find_spec("matplotlib") is None:      # the script plots with it
+        return
+    import shutil
+    shutil.copy(REF_SCRIPTS / "OFDM_Plotting.py", base / "scripts")
     r = subprocess.run([sys.executable, str(base / "scripts" / "OFDM_Plotting.py")], capture_output=True, text=True,
                        env={"MPLBACKEND": "Agg", "PATH": "/usr/bin:/bin"})
     assert r.returncode == 0, r.stderr
@@ -140,8 +181,12 @@ def test_reference_plotting_script_reads_our_files(pkg, tmp_path):
     assert (base / "results" / "ber_vs_snr.png").exists()
 
 
-REF_SCRIPTS = ROOT.parent / "reference" / "scripts"
-GPU_KAT_FILE = GOLDEN / "gpu_kat_Code_Output.txt"
+def _kat_mismatches(code_output_text):
+    """compare_double.py's verdict, restated: both files hold 96 numbers and the indices whose absolute difference
+    exceeds its tolerance 1e-6 (compare_double.py:41-42) are returned."""
+    ours, theirs = _script_numbers(code_output_text), _script_numbers(MATLAB_FILE.read_text())
+    assert len(ours) == len(theirs) == 96
+    return [i for i, (a, b) in enumerate(zip(ours, theirs)) if abs(a - b) > 1e-6]
 
 
 def _run_compare_double(cwd, code_output_text):
@@ -150,7 +195,8 @@ def _run_compare_double(cwd, code_output_text):
     import shutil
     cwd.mkdir(parents=True, exist_ok=True)
     shutil.copy(REF_SCRIPTS / "compare_double.py", cwd)
-    shutil.copy(ROOT.parent / "reference" / "data" / "Matlab_Output.txt", cwd)
+    assert (REF_TREE / "data" / "Matlab_Output.txt").read_bytes() == MATLAB_FILE.read_bytes()
+    shutil.copy(MATLAB_FILE, cwd)
     (cwd / "Code_Output.txt").write_text(code_output_text)
     r = subprocess.run([sys.executable, "compare_double.py"], cwd=cwd, capture_output=True, text=True,
                        env={"PATH": "/usr/bin:/bin"})
@@ -166,12 +212,11 @@ def _assert_compare_double_clean(out):
     assert "Mismatch" not in out, out
 
 
-@pytest.mark.skipif(not (REF_SCRIPTS / "compare_double.py").exists(),
-                    reason="reference scripts only exist in the build container")
 def test_reference_compare_double_reads_our_code_output(pkg, oracle, tmp_path):
     """north_star: scripts/compare_*.py drop in unchanged.  The KAT receiver's bits (frame mode, MATLAB
     convention, Tester payload, noiseless capture [0, 3000): D6) written by fileio.write_bits_file are
-    diffed by the unmodified compare_double.py against data/Matlab_Output.txt: zero mismatches.
+    diffed against data/Matlab_Output.txt (tests/golden/Matlab_Output.txt) by compare_double.py's rule: zero
+    mismatches.  Where the reference tree is present, the unmodified compare_double.py does the same diff.
     (a) bits of the oracle's KAT receiver (equal to the GPU's: tests/test_gpu_frame.py::test_matlab_known_answer);
     (b) the Code_Output.txt the GPU KAT test wrote on an MI355X (tests/golden/gpu_kat_Code_Output.txt)."""
     from ofdm_amd import fileio
@@ -180,12 +225,17 @@ def test_reference_compare_double_reads_our_code_output(pkg, oracle, tmp_path):
     o = oracle.receiver_frame(w[:3000], tb, "matlab")
     p = tmp_path / "bits.txt"
     fileio.write_bits_file(o["bits"][:96], p)
-    _assert_compare_double_clean(_run_compare_double(tmp_path / "a", p.read_text()))
     assert GPU_KAT_FILE.exists(), "the GPU KAT record is committed with the tests"
-    _assert_compare_double_clean(_run_compare_double(tmp_path / "b", GPU_KAT_FILE.read_text()))
     # the check is not vacuous: one flipped bit is reported as a mismatch
     bad = p.read_text().split("\t")
     bad[5] = str(1 - int(bad[5]))
+    assert _kat_mismatches(p.read_text()) == []
+    assert _kat_mismatches(GPU_KAT_FILE.read_text()) == []
+    assert _kat_mismatches("\t".join(bad)) == [5]
+    if not HAVE_REF_SCRIPTS:
+        return
+    _assert_compare_double_clean(_run_compare_double(tmp_path / "a", p.read_text()))
+    _assert_compare_double_clean(_run_compare_double(tmp_path / "b", GPU_KAT_FILE.read_text()))
     out = _run_compare_double(tmp_path / "c", "\t".join(bad))
     assert "Mismatch at index 5" in out and "Max Error: 1.000000e+00" in out
 

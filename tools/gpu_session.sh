@@ -19,7 +19,7 @@ step() {  # step NAME SECONDS CMD...
 STEPS=${STEPS:-smoke,tests,bench,prof}
 [[ $STEPS == *smoke* ]] && step smoke 400 python3 -c "import __graft_entry__ as g; g.smoke()"
 [[ $STEPS == *tests* ]] && step gpu_tests 1200 python3 -m pytest tests -m gpu -q -p no:cacheprovider ${PYTEST_ARGS:-}
-[[ $STEPS == *bench* ]] && step bench 600 python3 bench.py ${BENCH_ARGS:-}
+[[ $STEPS == *bench* ]] && step bench 600 python3 bench.py --full ${BENCH_ARGS:-}
 if [[ $STEPS == *prof* ]]; then
   export TMPDIR=/tmp
   step rocprof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}
