@@ -65,6 +65,17 @@ _SIGS = {
 }
 EXPORTS = tuple(_SIGS)
 
+# the extension header include/ofdm_mi355x_long.h (long messages: frames of up to 15 data symbols); the base
+# header's function list (EXPORTS) and ABI_VERSION do not change with it
+LONG_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_long.h"
+_LONG_SIGS = {
+    "ofdm_set_long_message": (C.c_int, [_V, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+}
+LONG_EXPORTS = tuple(_LONG_SIGS)
+MSG_MAX_CHARS = 96                 # ofdm_set_message
+LONG_MSG_MAX_CHARS = 180           # ofdm_set_long_message (OFDM_LONG_MSG_MAX_CHARS)
+LONG_MAX_DATA_SYMBOLS = 15
+
 
 class OfdmError(RuntimeError):
     pass
@@ -137,7 +148,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
         raise OfdmError(f"{p} not found: the HIP library must be built (build_lib.build()); "
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in {**_SIGS, **_LONG_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

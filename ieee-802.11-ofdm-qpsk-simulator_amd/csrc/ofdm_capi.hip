@@ -2,6 +2,7 @@
 // buffers, kernel timing and the symbol-mode sweep driver.  Host code only (the kernels are in
 // ofdm_symbol.hip / ofdm_frame.hip).
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -51,23 +52,38 @@ static void host_ltf_time(int conv, std::vector<float2> &out) {
 }
 
 // payload words: reference message (Data_Generator, OFDM.c:435-465) or MATLAB Tester (Tester.m:50-51)
-int payload_table(int payload, const std::string &message, uint32_t table[3 * MSG_MAX_FRAMES]) {
-    unsigned char bytes[MSG_MAX_CHARS];
+int payload_table_long(int payload, const std::string &message, uint32_t table[3 * LONG_MAX_FRAMES]) {
+    unsigned char bytes[LONG_MSG_MAX_CHARS];
     int frames;
     if (payload == OFDM_PAYLOAD_TESTER) {                       // 'A' x 11 + ' ' per 96 bits (Tester.m:50-51)
         frames = 2;
         for (int f = 0; f < 2; ++f)
             for (int c = 0; c < 12; ++c) bytes[12 * f + c] = c < 11 ? 0x41 : 0x20;
     } else {
-        const int len = (int)message.size();
+        const int len = std::min((int)message.size(), LONG_MSG_MAX_CHARS);
         frames = (8 * len + 95) / 96;                           // ceil(8 len / 96) (OFDM.c:439)
         for (int c = 0; c < 12 * frames; ++c) bytes[c] = c < len ? (unsigned char)message[c] : ' ';
     }
     for (int w = 0; w < 3 * frames; ++w)
         table[w] = ((uint32_t)bytes[4 * w] << 24) | ((uint32_t)bytes[4 * w + 1] << 16) |
                    ((uint32_t)bytes[4 * w + 2] << 8) | (uint32_t)bytes[4 * w + 3];
-    for (int w = 3 * frames; w < 3 * MSG_MAX_FRAMES; ++w) table[w] = 0u;
+    for (int w = 3 * frames; w < 3 * LONG_MAX_FRAMES; ++w) table[w] = 0u;
     return frames;
+}
+
+int payload_table(int payload, const std::string &message, uint32_t table[3 * MSG_MAX_FRAMES]) {
+    uint32_t t[3 * LONG_MAX_FRAMES];
+    const int frames = std::min(payload_table_long(payload, message, t), MSG_MAX_FRAMES);
+    std::memcpy(table, t, 3 * MSG_MAX_FRAMES * sizeof(uint32_t));
+    return frames;
+}
+
+int check_symbol_payload(const Ctx *c, int payload) {
+    if (payload == OFDM_PAYLOAD_MESSAGE && (int)c->message.size() > MSG_MAX_CHARS)
+        return set_error(OFDM_E_ARG, "symbol mode carries messages of at most %d data symbols; the message set by "
+                         "ofdm_set_long_message has %d (frame mode only)", MSG_MAX_FRAMES,
+                         (8 * (int)c->message.size() + 95) / 96);
+    return OFDM_OK;
 }
 
 int check_cfg(const ofdm_cfg *c) {
@@ -291,13 +307,26 @@ int ofdm_set_message(ofdm_ctx *ctx, const char *msg, int32_t len, int32_t *frame
     return OFDM_OK;
 }
 
+int ofdm_set_long_message(ofdm_ctx *ctx, const char *msg, int32_t len, int32_t *frames) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c || (len && !msg)) return set_error(OFDM_E_ARG, "bad message arguments");
+    if (len < 1 || len > LONG_MSG_MAX_CHARS)
+        return set_error(OFDM_E_ARG, "message length %d outside [1, %d] (at most %d data symbols per frame)", len,
+                         LONG_MSG_MAX_CHARS, LONG_MAX_FRAMES);
+    if (len <= MSG_MAX_CHARS) return ofdm_set_message(ctx, msg, len, frames);
+    c->message.assign(msg, (size_t)len);
+    c->wave_key = -1;
+    if (frames) *frames = (8 * len + 95) / 96;
+    return OFDM_OK;
+}
+
 int ofdm_payload_frames(ofdm_ctx *ctx, int payload, int32_t *frames) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (!c || !frames) return set_error(OFDM_E_ARG, "bad arguments");
     if (payload != OFDM_PAYLOAD_MESSAGE && payload != OFDM_PAYLOAD_TESTER)
         return set_error(OFDM_E_ARG, "payload %d has no fixed frame structure", payload);
-    uint32_t t[3 * MSG_MAX_FRAMES];
-    *frames = payload_table(payload, c->message, t);
+    uint32_t t[3 * LONG_MAX_FRAMES];
+    *frames = payload_table_long(payload, c->message, t);
     return OFDM_OK;
 }
 
@@ -355,7 +384,7 @@ static int check_tx(Ctx *c, const ofdm_cfg *cfg, int64_t n_frames, const void *d
     if (rc) return rc;
     if (n_frames < 0 || (n_frames && (!d_tx || !d_bits))) return set_error(OFDM_E_ARG, "bad tx buffers");
     if (n_frames > MAX_BATCH_FRAMES) return set_error(OFDM_E_ARG, "n_frames > %lld per batch", (long long)MAX_BATCH_FRAMES);
-    return OFDM_OK;
+    return check_symbol_payload(c, cfg->payload);
 }
 
 static TxArgs tx_args(Ctx *c, const ofdm_cfg *cfg, uint64_t first_frame, int64_t n_frames, void *d_tx, void *d_bits) {
@@ -421,6 +450,8 @@ static int rx_common(Ctx *c, const ofdm_cfg *cfg, const void *d_tx, const void *
     if (n_frames > MAX_BATCH_FRAMES) return set_error(OFDM_E_ARG, "n_frames > %lld per batch", (long long)MAX_BATCH_FRAMES);
     const bool dump = d_eq || d_dbits;
     if (dump && (!d_eq || !d_dbits)) return set_error(OFDM_E_ARG, "dump needs both d_eq and d_dbits");
+    if ((rc = check_symbol_payload(c, cfg->payload))) return rc;
+    if (c->nx_pending && (rc = check_symbol_payload(c, c->nx_cfg.payload))) return rc;
     // a pending next batch is written while this call reads (or, fused, builds) its own: the two must not share a
     // byte (groups of one launch would race on it)
     if (c->nx_pending && n_frames > 0) {
@@ -528,6 +559,7 @@ int ofdm_symbol_sweep(ofdm_ctx *ctx, const ofdm_cfg *cfg, const double *snr_db, 
     int rc = check_cfg(cfg);
     if (rc) return rc;
     if (n_snr < 0 || (n_snr && (!snr_db || !counters)) || n_frames < 0) return set_error(OFDM_E_ARG, "bad sweep args");
+    if ((rc = check_symbol_payload(c, cfg->payload))) return rc;
     if (n_snr == 0) return OFDM_OK;
     HIPOK(hipSetDevice(c->device));
     if (c->nx_pending) {             // a batch queued by the caller: built now, before the sweep's own batches

@@ -4,7 +4,7 @@
 #include <cstdarg>
 #include <string>
 #include <vector>
-#include "ofdm_mi355x.h"
+#include "ofdm_mi355x_long.h"
 
 namespace ofdm {
 
@@ -15,7 +15,18 @@ constexpr int MSG_MAX_FRAMES = 8;           // data symbols per frame-mode frame
 constexpr int MSG_MAX_CHARS = 12 * MSG_MAX_FRAMES;
 // payload words (MSB-first bits, 3 per data symbol) of the TESTER pattern or `message` padded with
 // ' ' to whole symbols (Data_Generator, OFDM.c:435-465); returns the data symbols per frame
+// (symbol mode's table: a message set through ofdm_set_long_message is cut at MSG_MAX_FRAMES symbols here, and the
+// symbol-mode entry points refuse it first, check_symbol_payload)
 int payload_table(int payload, const std::string &message, uint32_t table[3 * MSG_MAX_FRAMES]);
+// long messages (include/ofdm_mi355x_long.h, frame mode only): up to 15 data symbols per frame, the largest frame
+// whose matched-filter window (2,909 samples) fits the sync kernel's capture ring (2,973)
+constexpr int LONG_MAX_FRAMES = OFDM_LONG_MAX_DATA_SYMBOLS;
+constexpr int LONG_MSG_MAX_CHARS = OFDM_LONG_MSG_MAX_CHARS;
+static_assert(LONG_MSG_MAX_CHARS == 12 * LONG_MAX_FRAMES, "12 characters per data symbol");
+int payload_table_long(int payload, const std::string &message, uint32_t table[3 * LONG_MAX_FRAMES]);
+struct Ctx;
+// OFDM_E_ARG when `payload` is MESSAGE and the message set has more than MSG_MAX_FRAMES symbols (symbol mode)
+int check_symbol_payload(const Ctx *c, int payload);
 
 struct Ctx {
     enum { K_FFT = 0, K_TX = 1, K_RX = 2, K_FRAME = 3, NK = 4 };

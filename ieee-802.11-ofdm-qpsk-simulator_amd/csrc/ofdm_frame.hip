@@ -25,7 +25,7 @@
 
 // ofdm_frame_sym.hip / ofdm_frame_fix.hip include this file to instantiate one kernel each in a translation unit of
 // its own (their own scheduler flags, build_lib.SOURCE_FLAGS); everything else lives in this one
-#if defined(OFDM_FRAME_SYM_TU) || defined(OFDM_FRAME_FIX_TU) || defined(OFDM_FRAME_LONG_TU)
+#if defined(OFDM_FRAME_SYM_TU) || defined(OFDM_FRAME_FIX_TU) || defined(OFDM_FRAME_LONG_TU) || defined(OFDM_FRAME_XL_TU)
 #define OFDM_FRAME_AUX_TU 1
 #endif
 
@@ -40,6 +40,11 @@ __host__ __device__ constexpr int fr_len(int nd) { return 320 + 80 * nd; }
 __host__ __device__ constexpr int wave_len_for(int nd) { return (2 * fr_len(nd) + 20) * FR_REPS; }   // 2x + RRC tail
 inline int cap_len_for(int nd) { return (int)(wave_len_for(nd) * 0.307); }                          // OFDM.c:945
 constexpr int CAP_ABS_MAX = 6000;            // LDS budget of the capture (>= cap_len_for(FR_MAX_DATA) = 5955)
+// long messages (ofdm_set_long_message, include/ofdm_mi355x_long.h): 9..15 data symbols, the kernels of
+// ofdm_frame_xl.hip
+constexpr int FR_XL_MAX_DATA = LONG_MAX_FRAMES;
+constexpr int FR_XL_MAX = 320 + 80 * FR_XL_MAX_DATA;
+constexpr int CAP_XL_MAX = 9400;             // >= cap_len_for(FR_XL_MAX_DATA) = 9394
 
 // short training tones S_k at bins 6..58 (OFDM.c:483-490): +-1 on every 4th tone, times (1+j)
 __host__ __device__ constexpr int stf_sign(int bin) {
@@ -51,7 +56,7 @@ __host__ __device__ constexpr int stf_sign(int bin) {
 struct WaveArgs {
     float2 *wave;        // [wave_len_for(n_data)]
     double *power;       // mean |x|^2 over the waveform
-    uint32_t table[3 * FR_MAX_DATA];   // payload words of the data symbols
+    uint32_t table[3 * FR_XL_MAX_DATA];   // payload words of the data symbols
     int32_t n_data;
     float taps[21];
     float stf_scale;     // sqrt(13/6) as the float of OFDM.c:479
@@ -99,6 +104,15 @@ struct FrameArgs {
     const float *wave_re;           // real parts of one waveform copy (nfilt floats; ensure_wave), the capture's clean part
 };
 
+// The argument block of the long-message kernels (ofdm_frame_xl.hip): FrameArgs as it stands -- its size and layout
+// are part of the certified kernels' descriptors -- followed by the payload tables of up to FR_XL_MAX_DATA symbols
+// (f.table / f.dtable are not read by them)
+struct XlArgs {
+    FrameArgs f;
+    uint32_t table[3 * FR_XL_MAX_DATA];
+    uint32_t dtable[4 * FR_XL_MAX_DATA];
+};
+
 // x / d and x % d for 32-bit x and d >= 1: with m = floor((2^32 - 1) / d) >= (2^32 - d) / d,
 // x / d - 1 < x / d - x / 2^32 <= x m / 2^32 <= x / d, so t = mulhi(x, m) is the quotient or one less and one
 // correction step finishes it.  On wave-uniform operands it stays on the scalar unit (the compiler's udiv
@@ -134,8 +148,8 @@ constexpr bool FRAME_STAMPS_BUILD = false;
 #ifndef OFDM_FRAME_AUX_TU
 template <int CONV>
 __global__ __launch_bounds__(256) void frame_wave_kernel(WaveArgs a) {
-    __shared__ float2 T[2 + FR_MAX_DATA][64];   // STF, LTF, data time symbols
-    __shared__ float2 fr[FR_MAX];
+    __shared__ float2 T[2 + FR_XL_MAX_DATA][64];   // STF, LTF, data time symbols
+    __shared__ float2 fr[FR_XL_MAX];
     __shared__ double red[256];
     const int tid = threadIdx.x;
     const int nfr = fr_len(a.n_data), nos = 2 * nfr, nfilt = nos + 20;
@@ -491,6 +505,28 @@ __host__ __device__ inline size_t frame_lds_bytes(int cap_len, int n_data, int n
                                                   int waves = SYNC_WAVES) {
     return (size_t)n_snr * acc_slots(word_stats) * 8 + (((size_t)imt_len * 4 + 15) & ~size_t(15)) +
            (size_t)waves * wave_region_floats(cap_len, n_data) * 4;
+}
+
+// ---- long messages (ofdm_frame_xl.hip): detection in rounds of 64 lanes x XL_CHUNK positions, any number of them
+// (frame_sync_long_kernel's rounds), so that the ring kernel and the whole-capture kernel start every lane's sliding
+// sums at the same positions and agree to the bit
+constexpr int XL_CHUNK = 31;
+constexpr int XL_ROUND = 64 * XL_CHUNK;               // 1,984 positions per round
+constexpr int XL_PIECE = XL_ROUND + 47;               // a round's samples
+constexpr int XL_MAXR = 5;                            // rounds at most: Lc <= CAP_XL_MAX - 47 = 9,353 <= 5 x 1,984
+constexpr int XL_RING = 2976, XL_EXT = 96;            // the ring kernel's capture ring (floats) and its mirror
+constexpr int XL_RING_REGION = XL_RING + XL_EXT;      // 3,072 floats = 12,288 B per wave
+constexpr int XL_RING_W = 11;                         // ring kernel waves per block (one block per CU)
+constexpr int XL_TABLE_REACH = 2048;                  // its table past one period: a detection round's 63 x 31 + 80 floats
+static_assert(XL_MAXR * XL_ROUND + 47 >= CAP_XL_MAX, "XL_MAXR detection rounds cover every capture");
+// the whole-capture kernel's region (floats, a multiple of 4): the capture from float (rx_start & 3), the 80 floats the
+// last position's lane loads (up to L + 32) and the matched-filter runs' last window (up to L + 8)
+__host__ __device__ inline int xl_cap_region(int cap_len) { return (cap_len + 43) & ~3; }
+__host__ __device__ inline bool xl_fr_in_capture(int cap_len, int n_data) {
+    return xl_cap_region(cap_len) >= 6 * fr_len(n_data) + 24;
+}
+__host__ __device__ inline int xl_region_floats(int cap_len, int n_data) {
+    return xl_cap_region(cap_len) + (xl_fr_in_capture(cap_len, n_data) ? 0 : 2 * fr_len(n_data));
 }
 
 // LDS ordering between the lanes of one wave (no block barrier: the other waves run other items)
@@ -1792,7 +1828,15 @@ void launch_frame_long(hipStream_t st, const FrameArgs &a, dim3 grid, size_t lds
     hipLaunchKernelGGL((frame_sync_long_kernel<LONG_W>), grid, dim3(64 * LONG_W), lds, st, a);
 }
 }  // namespace ofdm
+#elif defined(OFDM_FRAME_XL_TU)
+}  // namespace ofdm: the long-message kernels follow the include in ofdm_frame_xl.hip
 #else
+// ofdm_frame_xl.hip: the long-message kernels (9..15 data symbols) and their launchers
+const void *frame_ring_xl_kernel_ptr();
+const void *frame_whole_xl_kernel_ptr();
+void launch_frame_ring_xl(hipStream_t st, const XlArgs &a, dim3 grid, size_t lds);
+void launch_frame_whole_xl(hipStream_t st, const XlArgs &a, dim3 grid, size_t lds);
+void launch_frame_sym_xl(hipStream_t st, const XlArgs &a, int cus);
 void launch_frame_sym(hipStream_t st, const FrameArgs &a, int cus);     // ofdm_frame_sym.hip
 const void *frame_fix_kernel();                                         // ofdm_frame_fix.hip
 void launch_frame_fix(hipStream_t st, const FrameArgs &a, dim3 grid, size_t lds);
@@ -1848,7 +1892,7 @@ static int ensure_wave(Ctx *c, int conv, int payload) {
     const int key = conv * 4 + payload;      // ofdm_set_message resets the key
     if (c->wave_key == key) return OFDM_OK;
     WaveArgs a{};
-    a.n_data = payload_table(payload, c->message, a.table);
+    a.n_data = payload_table_long(payload, c->message, a.table);
     const int len = wave_len_for(a.n_data);
     // [len] float2 waveform | power (64 B) | real parts of one copy (len / FR_REPS floats, 16-B aligned)
     int rc = c->ensure(&c->d_wave, &c->cap_wave, (size_t)len * sizeof(float2) + 64 + (size_t)len / FR_REPS * sizeof(float));
@@ -1877,13 +1921,16 @@ static int capture_len(const Ctx *c, const ofdm_rx_opts *o) { return o->cap_len 
 static int check_opts(const Ctx *c, const ofdm_rx_opts *o) {
     if (!o) return set_error(OFDM_E_ARG, "opts is NULL");
     const int L = capture_len(c, o);
-    if (L < 400 || L > CAP_ABS_MAX || L > c->wave_len)
-        return set_error(OFDM_E_ARG, "cap_len %d must be in [400, min(%d, waveform %d)]", L, CAP_ABS_MAX, c->wave_len);
+    // frames of 9..15 data symbols (ofdm_set_long_message) run the kernels of ofdm_frame_xl.hip, captures up to CAP_XL_MAX
+    const int cap_max = c->wave_frames > FR_MAX_DATA ? CAP_XL_MAX : CAP_ABS_MAX;
+    if (L < 400 || L > cap_max || L > c->wave_len)
+        return set_error(OFDM_E_ARG, "cap_len %d must be in [400, min(%d, waveform %d)]", L, cap_max, c->wave_len);
     if (o->fixed_start > c->wave_len - L) return set_error(OFDM_E_ARG, "fixed_start beyond the waveform");
     return OFDM_OK;
 }
 
-static void fill_frame_args(FrameArgs &a, Ctx *c, const ofdm_rx_opts *o, int noise, uint64_t seed, int payload) {
+static void fill_frame_args(XlArgs &xa, Ctx *c, const ofdm_rx_opts *o, int noise, uint64_t seed, int payload) {
+    FrameArgs &a = xa.f;
     a.wave = (const float2 *)c->d_wave;
     a.wave_re = wave_re_of(c, c->wave_len);
     a.cap_len = capture_len(c, o);
@@ -1894,8 +1941,12 @@ static void fill_frame_args(FrameArgs &a, Ctx *c, const ofdm_rx_opts *o, int noi
     a.wave_len = c->wave_len;
     a.k0 = (uint32_t)seed;
     a.k1 = (uint32_t)(seed >> 32);
-    a.n_data = payload_table(payload, c->message, a.table);
-    for (int d = 0; d < a.n_data; ++d) demap_words(a.table + 3 * d, a.dtable + 4 * d);
+    // the payload tables: up to FR_XL_MAX_DATA symbols in the long block, the first FR_MAX_DATA also where the
+    // kernels of 1..8 symbols read them
+    a.n_data = payload_table_long(payload, c->message, xa.table);
+    for (int d = 0; d < a.n_data; ++d) demap_words(xa.table + 3 * d, xa.dtable + 4 * d);
+    std::memcpy(a.table, xa.table, sizeof(a.table));
+    std::memcpy(a.dtable, xa.dtable, sizeof(a.dtable));
     a.word_stats = o->word_stats ? 1 : 0;
     // the lazy capture's equivalence test runs the same sweep with it switched off (tests/test_gpu_frame.py)
     a.no_lazy = getenv("OFDM_FRAME_NO_LAZY") != nullptr;
@@ -1915,14 +1966,15 @@ static int32_t word_bits(double mn, double mx) {
 constexpr int64_t FRAME_CHUNK_ITEMS = int64_t(1) << FRAME_CHUNK_LOG2;
 // items per chunk for n_data data symbols: 2^23, capped so that the hand-off buffer holds no more windows than the
 // reference message's 2^23 items do (1 + n_data windows of 512 B per item: 12 GiB; ADVICE r3: 8-symbol messages
-// would otherwise take 38 GiB)
+// would otherwise take 38 GiB; 15 symbols, 16 windows per item: 2^23 x 3 / 16 = 1,572,864 items, the same 12 GiB)
 static int64_t frame_chunk_items(int n_data) {
     return std::min<int64_t>(FRAME_CHUNK_ITEMS, FRAME_CHUNK_ITEMS * 3 / (1 + n_data));
 }
 constexpr int64_t FRAME_CHUNK_MIN = int64_t(1) << 16;    // halving stops here when the buffer cannot be allocated
 
 // K4b then K4b' over a.n_items items starting at a.item0, through the context's hand-off buffer
-static int run_frame_chunk(Ctx *c, FrameArgs &a) {
+static int run_frame_chunk(Ctx *c, XlArgs &xa) {
+    FrameArgs &a = xa.f;
     const int nw = 1 + a.n_data;
     if (a.n_snr < 1 || a.n_items < 0 || a.n_items + a.n_snr + FRAME_ITEM_RUN > (int64_t(1) << 31))
         return set_error(OFDM_E_ARG, "frame chunk: items or SNR points out of range");
@@ -1951,30 +2003,66 @@ static int run_frame_chunk(Ctx *c, FrameArgs &a) {
     // statistics) runs the instantiation with that geometry folded in; OFDM_FRAME_GENERIC=1 forces the generic
     // one (the equivalence test)
     const int64_t runs = (a.n_items + FRAME_ITEM_RUN - 1) / FRAME_ITEM_RUN;
+    const bool plain = !a.ext && !a.dbg_res && !a.dbg_ints && !a.dbg_bits && !a.dbg_eq && !a.dbg_corr && !a.dbg_frame &&
+                       !a.word_stats;        // a sweep of generated captures: no dumps, no word-length statistics
+    if (a.n_data > FR_MAX_DATA) {
+        // Frames of 9..15 data symbols (ofdm_frame_xl.hip).  The ring kernel (one 12-KB capture ring per wave, 11 waves
+        // per CU) runs the plain sweeps whose matched-filter window fits its ring and whose LDS fits the CU; the
+        // whole-capture kernel (one-wave blocks, the capture's real parts resident) runs everything else: external
+        // captures, dumps, word-length statistics, short user captures, OFDM_FRAME_NO_LONG=1 (the equivalence test)
+        const int Lc = a.cap_len - 47;
+        a.imt_len = a.im_period + XL_TABLE_REACH;
+        const size_t lds_r = (size_t)a.n_snr * 2 * 8 + (((size_t)a.imt_len * 4 + 15) & ~size_t(15)) +
+                             (size_t)XL_RING_W * XL_RING_REGION * 4;
+        // (4 or 5 detection rounds: the default captures of 9..15 symbols; the window [p + 140, p + 2 (nfr - 1) + 10]
+        // of 2 nfr - 131 samples inside the XL_RING - 3 the ring keeps; fr[] inside the region)
+        const bool ring = plain && Lc > 3 * XL_ROUND && Lc <= XL_MAXR * XL_ROUND && 2 * fr_len(a.n_data) - 131 <= XL_RING - 3 &&
+                          2 * fr_len(a.n_data) <= XL_RING_REGION && lds_r <= FRAME_LDS_PER_CU &&
+                          !getenv("OFDM_FRAME_NO_LONG") && !FRAME_STAMPS_BUILD;
+        if (ring) {
+            a.region_floats = XL_RING_REGION;
+            const dim3 gr(occupancy_grid(frame_ring_xl_kernel_ptr(), 64 * XL_RING_W, lds_r, c->cus,
+                                         (runs + XL_RING_W - 1) / XL_RING_W, 1));
+            launch_frame_ring_xl(c->stream, xa, gr, lds_r);
+        } else {
+            a.imt_len = (a.ext ? a.cap_len : a.im_period) + IMT_EXT;
+            a.fr_in_cap = xl_fr_in_capture(a.cap_len, a.n_data);
+            a.region_floats = xl_region_floats(a.cap_len, a.n_data);
+            const size_t lds_w = (size_t)a.n_snr * acc_slots(a.word_stats) * 8 + (((size_t)a.imt_len * 4 + 15) & ~size_t(15)) +
+                                 (size_t)a.region_floats * 4;
+            if (lds_w > FRAME_LDS_PER_CU)
+                return set_error(OFDM_E_ARG, "frame chunk: %zu B of LDS for a capture of %d samples", lds_w, a.cap_len);
+            const dim3 gw(occupancy_grid(frame_whole_xl_kernel_ptr(), 64, lds_w, c->cus, runs, 1));
+            launch_frame_whole_xl(c->stream, xa, gw, lds_w);
+        }
+        launch_frame_sym_xl(c->stream, xa, c->cus);
+        HIPOK(hipGetLastError());
+        return OFDM_OK;
+    }
     // long captures (frames of >= 5 data symbols): frame_sync_long_kernel keeps one detection round's piece per wave, not
     // the whole capture (3 waves per SIMD instead of 1); sweeps only.  OFDM_FRAME_NO_LONG=1 forces the generic kernel
     // (the equivalence test)
-    const bool is_long = a.cap_len > FRAME_LONG_MIN_CAP && a.cap_len - 47 <= 3 * 64 * 31 && !a.ext && !a.dbg_res &&
-                         !a.dbg_ints && !a.dbg_bits && !a.dbg_eq && !a.dbg_corr && !a.dbg_frame && !a.word_stats &&
+    // (its LDS grows with the SNR points of the launch: 8 symbols at 28..64 points are past the CU's 160 KiB and run
+    // the generic kernel)
+    const size_t lds_l = (size_t)a.n_snr * 2 * 8 + ((((size_t)a.im_period + LONG_TABLE_REACH) * 4 + 15) & ~size_t(15)) +
+                         (size_t)LONG_W * FRAME_LONG_REGION * 4;
+    const bool is_long = a.cap_len > FRAME_LONG_MIN_CAP && a.cap_len - 47 <= 3 * 64 * 31 && plain &&
                          2 * fr_len(a.n_data) + 40 <= FRAME_LONG_REGION && !getenv("OFDM_FRAME_NO_LONG") &&
-                         !FRAME_STAMPS_BUILD;
+                         !FRAME_STAMPS_BUILD && lds_l <= FRAME_LDS_PER_CU;
     // every capture routed here has Lc > 2 x 64 x 31: the long kernel always runs three detection rounds (its R == 2
     // branches are unreachable; they stay so that the PMC-certified code object does not move)
     static_assert(FRAME_LONG_MIN_CAP - 47 >= 2 * 64 * 31, "long captures take three detection rounds");
     if (is_long) {
         a.region_floats = FRAME_LONG_REGION;
         a.imt_len = a.im_period + LONG_TABLE_REACH;           // the long kernel's wrap-free table
-        const size_t lds_l = (size_t)a.n_snr * 2 * 8 + (((size_t)a.imt_len * 4 + 15) & ~size_t(15)) +
-                             (size_t)LONG_W * FRAME_LONG_REGION * 4;
         const dim3 gl(occupancy_grid(frame_long_kernel(), 64 * LONG_W, lds_l, c->cus, (runs + LONG_W - 1) / LONG_W, 1));
         launch_frame_long(c->stream, a, gl, lds_l);
         launch_frame_sym(c->stream, a, c->cus);
         HIPOK(hipGetLastError());
         return OFDM_OK;
     }
-    const bool fixed = a.n_data == 2 && a.cap_len == cap_len_for(2) && a.wave_len == wave_len_for(2) && !a.ext &&
-                       !a.dbg_res && !a.dbg_ints && !a.dbg_bits && !a.dbg_eq && !a.dbg_corr && !a.dbg_frame &&
-                       !a.word_stats && !getenv("OFDM_FRAME_GENERIC");
+    const bool fixed = a.n_data == 2 && a.cap_len == cap_len_for(2) && a.wave_len == wave_len_for(2) && plain &&
+                       !getenv("OFDM_FRAME_GENERIC");
     // Long captures (8-symbol messages: 24 KB per wave) could run one-wave blocks, which fit five per CU where
     // one four-wave block fits; but five waves on four SIMDs leave three SIMDs with one wave each, and
     // the 8-symbol sweep measured 4.07e8 with one-wave blocks against 4.16e8 with four-wave ones (round 4,
@@ -2053,13 +2141,14 @@ int ofdm_receiver(ofdm_ctx *ctx, const float *capture, const ofdm_rx_opts *opts,
     // scratch: capture | counters | res | ints | bits | eq
     const size_t off_cnt = ((size_t)L * sizeof(float2) + 255) & ~size_t(255);
     const size_t off_res = off_cnt + OFDM_NCOUNTERS * 8, off_int = off_res + 16, off_bits = off_int + 16;
-    const size_t off_eq = off_bits + 4 * 3 * FR_MAX_DATA, total = off_eq + 48 * FR_MAX_DATA * sizeof(float2);
+    const size_t off_eq = off_bits + 4 * 3 * FR_XL_MAX_DATA, total = off_eq + 48 * FR_XL_MAX_DATA * sizeof(float2);
     if ((rc = c->ensure(&c->d_scratch2, &c->cap_scratch2, total))) return rc;
     char *base = (char *)c->d_scratch2;
     HIPOK(hipMemcpyAsync(base, capture, (size_t)L * sizeof(float2), hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemsetAsync(base + off_cnt, 0, total - off_cnt, c->stream));
-    FrameArgs a{};
-    fill_frame_args(a, c, opts, OFDM_NOISE_NONE, 0, payload);
+    XlArgs xa{};
+    FrameArgs &a = xa.f;
+    fill_frame_args(xa, c, opts, OFDM_NOISE_NONE, 0, payload);
     a.ext = (const float2 *)base;
     a.first_trial = 0;
     a.n_trials = 1;
@@ -2074,13 +2163,13 @@ int ofdm_receiver(ofdm_ctx *ctx, const float *capture, const ofdm_rx_opts *opts,
     a.n_items = 1;
     a.add_totals = 1;
     c->tic(Ctx::K_FRAME);
-    rc = run_frame_chunk(c, a);
+    rc = run_frame_chunk(c, xa);
     c->toc();
     if (rc) return rc;
     float res[4];
     int32_t ints[4];
-    uint32_t words[3 * FR_MAX_DATA];
-    float2 eq[48 * FR_MAX_DATA];
+    uint32_t words[3 * FR_XL_MAX_DATA];
+    float2 eq[48 * FR_XL_MAX_DATA];
     HIPOK(hipMemcpyAsync(res, base + off_res, 16, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipMemcpyAsync(ints, base + off_int, 16, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipMemcpyAsync(words, base + off_bits, sizeof(words), hipMemcpyDeviceToHost, c->stream));
@@ -2123,8 +2212,9 @@ int ofdm_frame_sweep(ofdm_ctx *ctx, const ofdm_cfg *cfg, const ofdm_rx_opts *opt
     }
     int32_t *dp = packet_idx ? (int32_t *)((char *)c->d_cnt + ((cbytes + 255) & ~size_t(255))) : nullptr;
     for (int q0 = 0; q0 < n_snr; q0 += OFDM_MAX_SNR) {
-        FrameArgs a{};
-        fill_frame_args(a, c, opts, cfg->noise, cfg->seed, cfg->payload);
+        XlArgs xa{};
+        FrameArgs &a = xa.f;
+        fill_frame_args(xa, c, opts, cfg->noise, cfg->seed, cfg->payload);
         a.first_trial = first_trial;
         a.n_trials = n_trials;
         a.n_snr = std::min(OFDM_MAX_SNR, n_snr - q0);
@@ -2147,7 +2237,7 @@ int ofdm_frame_sweep(ofdm_ctx *ctx, const ofdm_cfg *cfg, const ofdm_rx_opts *opt
             a.item0 = i0;
             a.n_items = std::min(chunk, items - i0);
             a.add_totals = i0 + a.n_items >= items;
-            rc = run_frame_chunk(c, a);
+            rc = run_frame_chunk(c, xa);
             if (rc == OFDM_E_NOMEM && chunk > FRAME_CHUNK_MIN) {   // nothing launched yet: a smaller buffer
                 (void)hipGetLastError();
                 chunk /= 2;

@@ -186,13 +186,21 @@ class Engine:
         check(self.lib, self.lib.ofdm_set_message(self.ctx, b, len(b), C.byref(n)), "set_message")
         return n.value
 
+    def set_long_message(self, message: str | bytes) -> int:
+        """MESSAGE payload text of up to 180 characters (15 data symbols; ofdm_set_long_message, frame mode only for
+        more than 96); up to 96 characters it is set_message itself.  Returns the data symbols per frame."""
+        b = message.encode("latin-1") if isinstance(message, str) else bytes(message)
+        n = C.c_int32()
+        check(self.lib, self.lib.ofdm_set_long_message(self.ctx, b, len(b), C.byref(n)), "set_long_message")
+        return n.value
+
     def payload_frames(self, payload: str = "message") -> int:
         n = C.c_int32()
         check(self.lib, self.lib.ofdm_payload_frames(self.ctx, abi.PAYLOAD[payload], C.byref(n)), "payload_frames")
         return n.value
 
     def transmitter(self, conv: str = "c", payload: str = "message", float_taps: bool = True) -> np.ndarray:
-        cap = abi.wave_len(8)
+        cap = abi.wave_len(self.payload_frames(payload))
         buf = np.zeros(2 * cap, np.float32)
         n = C.c_int32()
         check(self.lib, self.lib.ofdm_transmitter(self.ctx, abi.CONV[conv], abi.PAYLOAD[payload], int(float_taps),

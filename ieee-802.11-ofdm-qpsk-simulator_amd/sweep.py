@@ -38,12 +38,20 @@ from .fileio import write_reference_outputs
 REF_SNR = np.arange(6.0, 41.0, 1.0)        # OFDM.c:18, 1197
 
 
+def set_message(engine: Engine, message: str | bytes) -> int:
+    """OFDM.c:20-21 `message`: up to 96 characters through the base entry, longer ones (up to 180 characters, 15 data
+    symbols, frame mode) through the extension header's ofdm_set_long_message."""
+    if len(message) > abi.MSG_MAX_CHARS:
+        return engine.set_long_message(message)
+    return engine.set_message(message)
+
+
 def run_sweep(engine: Engine, snr_db, trials: int, mode: str = "frame", seed: int = 0x80211A,
               payload: str | None = None, est: str = "ls", noise: str = "real", channel: str = "awgn",
               conv: str = "c", rank: int = 0, world: int = 1, message: str | None = None) -> SweepResult:
     snr = np.asarray(snr_db, np.float64)
     if message is not None:
-        engine.set_message(message)             # OFDM.c:20 `message`, framed by Data_Generator
+        set_message(engine, message)            # OFDM.c:20 `message`, framed by Data_Generator
     start, end = dist.shard_range(trials, rank, world)
     if mode == "frame":
         cfg = abi.make_cfg(seed=seed, conv=conv, payload=payload or "message", noise=noise)
@@ -101,7 +109,8 @@ def main(argv=None):
     ap.add_argument("--channel", choices=["awgn", "rayleigh4"], default="awgn")
     ap.add_argument("--conv", choices=["c", "matlab"], default="c")
     ap.add_argument("--payload", choices=["random", "message", "tester"])
-    ap.add_argument("--message", help="MESSAGE payload text (default: OFDM.c:20), up to 96 characters")
+    ap.add_argument("--message", help="MESSAGE payload text (default: OFDM.c:20), up to 180 characters in frame mode (15 data "
+                                      "symbols, e.g. the 171-character message of OFDM.c:21), up to 96 in symbol mode")
     ap.add_argument("--evm", choices=["trial", "finite", "pooled"], default="trial",
                     help="EVM files: mean of per-trial EVM_dB (the reference's statistic, -inf after the slicer "
                          "once one trial is clean), the same with the post-slicer mean over finite trials, or pooled")
@@ -123,7 +132,7 @@ def received_messages(snr_db, message: str | None = None, seed: int = 0x80211A, 
     -- yielding the console text the reference prints (OFDM.c:1177-1181)."""
     with Engine(device) as eng:
         if message is not None:
-            eng.set_message(message)
+            set_message(eng, message)
         nd = eng.payload_frames("message")
         w = eng.transmitter("c", "message")
         L = abi.capture_len(nd)

@@ -172,8 +172,8 @@ int ofdm_symbol_sweep(ofdm_ctx *ctx, const ofdm_cfg *cfg, const double *snr_db, 
 
 /* ---- payload text (SURVEY §8(f) message mode) ----
  * MESSAGE payload = `msg` (default "Hey! I am Vivaswan", OFDM.c:20), MSB-first bytes padded with ' '
- * to ceil(8 len / 96) data symbols per frame (Data_Generator, OFDM.c:435-465); 1 <= len <= 96 (frame
- * mode carries at most 8 data symbols).  Symbol mode uses message symbol s mod frames for data
+ * to ceil(8 len / 96) data symbols per frame (Data_Generator, OFDM.c:435-465); 1 <= len <= 96 (8 data
+ * symbols; frame mode takes up to 180 characters through ofdm_mi355x_long.h).  Symbol mode uses message symbol s mod frames for data
  * symbol s.  `frames` (optional) receives the data symbols per frame. */
 int ofdm_set_message(ofdm_ctx *ctx, const char *msg, int32_t len, int32_t *frames);
 /* data symbols per frame of a fixed payload: MESSAGE (current message) or TESTER (2) */
