@@ -76,6 +76,16 @@ MSG_MAX_CHARS = 96                 # ofdm_set_message
 LONG_MSG_MAX_CHARS = 180           # ofdm_set_long_message (OFDM_LONG_MSG_MAX_CHARS)
 LONG_MAX_DATA_SYMBOLS = 15
 
+# the extension header include/ofdm_mi355x_captures.h (Receiver() over a device-resident batch of caller-supplied
+# captures); EXPORTS, LONG_EXPORTS and ABI_VERSION do not change with it
+CAPTURES_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_captures.h"
+_CAPTURES_SIGS = {
+    "ofdm_receive_captures": (C.c_int, [_V, _V, C.c_int64, C.c_int64, _V, C.c_int, _V, _V, _V, _V]),
+}
+CAPTURES_EXPORTS = tuple(_CAPTURES_SIGS)
+CAPTURE_MAX_LEN = 9400             # OFDM_CAPTURE_MAX_LEN
+CAPTURE_SYNC_FAIL, CAPTURE_OOB = 1, 2      # ofdm_capture_result.flags
+
 
 class OfdmError(RuntimeError):
     pass
@@ -93,6 +103,42 @@ class RxOpts(C.Structure):
     _fields_ = [("cap_len", C.c_int32), ("float_cfo", C.c_int32), ("matlab_slicer", C.c_int32),
                 ("float_taps", C.c_int32), ("fixed_start", C.c_int32), ("word_stats", C.c_int32),
                 ("reserved", C.c_int32 * 2)]
+
+
+class CaptureResult(C.Structure):
+    """ofdm_capture_result (48 bytes, one per capture)"""
+    _fields_ = [("packet_idx", C.c_int32), ("flags", C.c_int32), ("bit_err", C.c_int32), ("post_axis_err", C.c_int32),
+                ("evm_pre_sum", C.c_float), ("evm_db_pre", C.c_float), ("evm_db_post", C.c_float), ("ber", C.c_float),
+                ("cfo_coarse_hz", C.c_float), ("cfo_fine_hz", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+def capture_result_dtype():
+    """numpy structured dtype of ofdm_capture_result (same names, offsets and size as CaptureResult)"""
+    import numpy as np  # noqa: PLC0415
+    return np.dtype([("packet_idx", "<i4"), ("flags", "<i4"), ("bit_err", "<i4"), ("post_axis_err", "<i4"),
+                     ("evm_pre_sum", "<f4"), ("evm_db_pre", "<f4"), ("evm_db_post", "<f4"), ("ber", "<f4"),
+                     ("cfo_coarse_hz", "<f4"), ("cfo_fine_hz", "<f4"), ("reserved", "<i4", (2,))])
+
+
+def reduce_capture_records(rec, frames: int):
+    """The counters row ofdm_receive_captures adds for these records (the header's rule): int64 [NCOUNTERS]."""
+    import numpy as np  # noqa: PLC0415
+    rec = np.asarray(rec)
+    out = np.zeros(NCOUNTERS, np.int64)
+    n = len(rec)
+    out[C_FRAMES], out[C_SYMBOLS], out[C_BITS], out[C_EVM_TERMS] = n, n * frames, 96 * frames * n, 48 * frames * n
+    out[C_BIT_ERR] = rec["bit_err"].astype(np.int64).sum()
+    out[C_FRAME_ERR] = int((rec["bit_err"] > 0).sum())
+    out[C_SYNC_FAIL] = int((rec["flags"] & CAPTURE_SYNC_FAIL != 0).sum())
+    out[C_OOB] = int((rec["flags"] & CAPTURE_OOB != 0).sum())
+    out[C_EVM_POST_AXIS] = rec["post_axis_err"].astype(np.int64).sum()
+    q = lambda v: np.rint(v.astype(np.float64) * EVM_Q_SCALE).astype(np.int64)    # llrint of the stored fp32 value
+    out[C_EVM_PRE_Q] = q(rec["evm_pre_sum"]).sum()
+    out[C_EVMDB_PRE_Q] = q(rec["evm_db_pre"]).sum()
+    fin = np.isfinite(rec["evm_db_post"])
+    out[C_EVMDB_POST_Q] = q(rec["evm_db_post"][fin]).sum()
+    out[C_EVMDB_POST_FINITE] = int(fin.sum())
+    return out
 
 
 def make_cfg(seed: int = 0x80211A, conv: str = "c", payload: str = "random", est: str = "ls",
@@ -148,7 +194,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
         raise OfdmError(f"{p} not found: the HIP library must be built (build_lib.build()); "
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**_SIGS, **_LONG_SIGS}.items():
+    for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,83 @@
+"""Impaired captures for Engine.receive_captures (torch plumbing only; the receiver is the HIP kernel).
+
+make_captures() cuts captures out of the repeated frame waveform (Transmitter(), OFDM.c:467-618) after an optional
+multipath FIR, a carrier frequency offset and AWGN -- the impairments the reference's receiver spends its coarse / fine
+CFO estimation (OFDM.c:773-828) and its per-subcarrier equaliser on, and that the in-kernel capture generator of
+ofdm_frame_sweep (real-only AWGN over the clean waveform) cannot produce.  It runs on whatever device `wave` is on,
+the CPU included.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+TS_OVERSAMPLED = 25e-9        # sample period of the waveform: 2 x 20 MHz (OFDM.c:16-17, oversampling 2)
+NOISE_KINDS = ("real", "complex", "none")
+
+
+def _torch():
+    import torch  # noqa: PLC0415
+    return torch
+
+
+def make_captures(wave, starts, snr_db, cfo_hz=0.0, taps=None, noise: str = "real", generator=None,
+                  cap_len: int | None = None):
+    """Captures [n, cap_len] (complex64, on wave's device) of the waveform `wave` (complex64 [len]).  In order:
+
+    1. `taps` (optional): a linear FIR at the oversampled rate over the whole repeated waveform, truncated to its
+       length: y[k] = sum_j taps[j] wave[k - j].
+    2. the rotation exp(j 2 pi cfo_hz k 25e-9) by the absolute waveform index k.
+    3. noise of variance mean|wave|^2 / 10^(snr_db / 10), measured on the unimpaired waveform as
+       Transmission_Over_Air does (OFDM.c:637-647): "real" carries all of it in the real part (what OFDM.c:651
+       does), "complex" splits it across both axes, "none" adds nothing.
+    4. the windows [start, start + cap_len).
+
+    starts, snr_db and cfo_hz broadcast against each other to the n captures.  cap_len None: int(0.307 len(wave))
+    (OFDM.c:945).  generator: a torch.Generator on wave's device for the noise."""
+    torch = _torch()
+    if noise not in NOISE_KINDS:
+        raise ValueError(f"noise must be one of {NOISE_KINDS}, got {noise!r}")
+    wave = torch.as_tensor(wave)
+    if wave.dim() != 1 or not wave.is_complex():
+        raise ValueError("wave must be a one-dimensional complex tensor")
+    wave = wave.to(torch.complex64)
+    dev, wl = wave.device, int(wave.shape[0])
+    L = int(wl * 0.307) if cap_len is None else int(cap_len)
+    st, snr, cfo = torch.broadcast_tensors(
+        torch.atleast_1d(torch.as_tensor(starts, device=dev)).to(torch.int64),
+        torch.atleast_1d(torch.as_tensor(snr_db, device=dev)).to(torch.float64),
+        torch.atleast_1d(torch.as_tensor(cfo_hz, device=dev)).to(torch.float64))
+    if st.numel() and (int(st.min()) < 0 or int(st.max()) + L > wl):
+        raise ValueError(f"capture windows of {L} samples must lie inside the {wl}-sample waveform")
+    power = float(torch.mean(wave.real.double() ** 2 + wave.imag.double() ** 2))        # OFDM.c:637-643
+    y = wave
+    if taps is not None:
+        h = np.asarray(taps, np.complex64).ravel()
+        y = torch.zeros_like(wave)
+        for j, hj in enumerate(h):
+            if hj != 0 and j < wl:
+                y[j:] += complex(hj) * wave[:wl - j]
+    k = st[:, None] + torch.arange(L, device=dev, dtype=torch.int64)[None, :]           # absolute waveform index
+    caps = y[k]
+    if bool((cfo != 0).any()):
+        rev = cfo[:, None] * k.double() * TS_OVERSAMPLED                                # phase in revolutions, fp64
+        ang = (2.0 * np.pi) * (rev - torch.round(rev))
+        caps = caps * torch.complex(torch.cos(ang), torch.sin(ang)).to(torch.complex64)
+    if noise != "none":
+        sigma = torch.sqrt(power / 10.0 ** (snr / 10.0))[:, None]                       # OFDM.c:645-651
+        n = st.shape[0]
+        if noise == "real":
+            g = torch.randn((n, L), generator=generator, device=dev, dtype=torch.float32)
+            nz = torch.complex(g * sigma.float(), torch.zeros_like(g))
+        else:
+            g = torch.randn((n, L, 2), generator=generator, device=dev, dtype=torch.float32)
+            nz = torch.view_as_complex((g * (sigma.float() * (0.5 ** 0.5))[..., None]).contiguous())
+        caps = caps + nz
+    return caps.contiguous()
+
+
+def parse_taps(text: str) -> np.ndarray:
+    """'1,0,0.4+0.3j' -> complex64 taps"""
+    return np.array([complex(t.strip()) for t in text.split(",") if t.strip()], np.complex64)
+
+
+__all__ = ["make_captures", "parse_taps", "TS_OVERSAMPLED"]

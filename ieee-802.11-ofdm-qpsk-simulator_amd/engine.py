@@ -3,7 +3,7 @@
 Mirrors the reference's three hot-path functions (src/OFDM.c):
     Transmitter()            OFDM.c:467-618   -> Engine.transmitter() / Engine.tx_frames()
     Transmission_Over_Air()  OFDM.c:635-655   -> Engine.transmission_over_air()
-    Receiver()               OFDM.c:941-1165  -> Engine.receiver() / Engine.rx_frames()
+    Receiver()               OFDM.c:941-1165  -> Engine.receiver() / Engine.rx_frames() / Engine.receive_captures()
 and main()'s SNR loop (OFDM.c:1187-1222) -> Engine.symbol_sweep() / Engine.frame_sweep().
 All arithmetic happens in the HIP kernels of libofdm_mi355x.so.
 """
@@ -233,6 +233,75 @@ class Engine:
                                                eq.ctypes.data_as(C.c_void_p)), "receiver")
         return dict(res=res, packet_idx=int(ints[0]), sync_fail=int(ints[1]), oob=int(ints[2]), frames=nd,
                     bits=bits, eq=eq.view(np.complex64).copy(), message=decode_message(bits))
+
+    def receive_captures(self, captures, mode: str = "c", payload: str = "message", want_bits: bool = True,
+                         want_eq: bool = False, counters=None) -> dict:
+        """Receiver() over a batch of caller-supplied captures (ofdm_receive_captures, include/ofdm_mi355x_captures.h):
+        one record per capture, the two CFO estimates included.
+
+        captures: a torch complex64 tensor [n, L >= cap_len] on this engine's device, used in place (its row stride
+        is the pitch; it is never written), or a numpy complex64 array of that shape, uploaded once.  Anything else
+        raises ValueError before any launch.  counters: an int64 device tensor of NCOUNTERS elements, added to.
+        Returns records (a structured array, abi.capture_result_dtype(); for torch input a dict of device tensors per
+        field), bits ([n, 96 D] int32), eq ([n, 48 D] complex64), messages (decode_message per row) -- bits, eq and
+        messages None when not asked for.  Outputs are allocated by torch on the current stream; only `messages`
+        (want_bits) and numpy results wait for the device."""
+        torch = _torch()
+        opts = make_rx_opts(mode)
+        nd = self.payload_frames(payload)
+        L = opts.cap_len or abi.capture_len(nd)
+        dev = torch.device("cuda", self.device)
+        from_numpy = isinstance(captures, np.ndarray)
+        if from_numpy:
+            if captures.dtype != np.complex64 or captures.ndim != 2:
+                raise ValueError(f"captures must be complex64 [n, L], got {captures.dtype} {captures.shape}")
+            if captures.shape[1] < L:
+                raise ValueError(f"captures hold {captures.shape[1]} samples, the receiver needs {L}")
+            t = torch.from_numpy(np.ascontiguousarray(captures)).to(dev)
+        elif torch.is_tensor(captures):
+            t = captures
+        else:
+            raise ValueError(f"captures must be a torch tensor or a numpy array, got {type(captures).__name__}")
+        if t.dtype != torch.complex64 or t.dim() != 2:
+            raise ValueError(f"captures must be complex64 [n, L], got {t.dtype} {tuple(t.shape)}")
+        if t.shape[1] < L:
+            raise ValueError(f"captures hold {t.shape[1]} samples, the receiver needs {L}")
+        if t.device != dev:
+            raise ValueError(f"captures are on {t.device}, the engine runs on {dev}")
+        n = int(t.shape[0])
+        if t.stride(1) != 1 or (n > 1 and t.stride(0) < L):
+            raise ValueError(f"captures need a unit inner stride and a row stride >= {L}, got strides {t.stride()}")
+        pitch = int(t.stride(0)) if n > 1 else max(int(t.shape[1]), L)
+        if counters is not None:
+            if not (torch.is_tensor(counters) and counters.dtype == torch.int64 and counters.device == dev
+                    and counters.numel() == abi.NCOUNTERS and counters.is_contiguous()):
+                raise ValueError("counters must be a contiguous int64 device tensor of NCOUNTERS elements")
+        rec = torch.empty((n, C.sizeof(abi.CaptureResult)), dtype=torch.uint8, device=dev)
+        words = torch.empty((n, 3 * nd), dtype=torch.int32, device=dev) if want_bits else None
+        eq = torch.empty((n, 48 * nd), dtype=torch.complex64, device=dev) if want_eq else None
+        if n:
+            check(self.lib, self.lib.ofdm_receive_captures(
+                self.ctx, _ptr(t), n, pitch, C.byref(opts), abi.PAYLOAD[payload], _ptr(rec),
+                None if words is None else _ptr(words), None if eq is None else _ptr(eq),
+                None if counters is None else _ptr(counters)), "receive_captures")
+        bits = None
+        if want_bits:
+            sh = torch.arange(31, -1, -1, dtype=torch.int32, device=dev)
+            bits = ((words.unsqueeze(-1) >> sh) & 1).reshape(n, 96 * nd)              # MSB first
+        dt = abi.capture_result_dtype()
+        if from_numpy:
+            records = rec.cpu().numpy().view(dt).reshape(n)
+            bits = None if bits is None else bits.cpu().numpy()
+            eq = None if eq is None else eq.cpu().numpy()
+        else:
+            w = rec.view(torch.int32)                                                 # [n, 12]
+            records = {name: (w[:, k] if dt[name].kind == "i" else w[:, k].view(torch.float32))
+                       for k, name in enumerate(dt.names[:10])}
+        messages = None
+        if want_bits:
+            host = bits if from_numpy else bits.cpu().numpy()
+            messages = [decode_message(row) for row in host]
+        return dict(records=records, bits=bits, eq=eq, messages=messages, frames=nd, cap_len=L)
 
     def word_length_report(self, capture: np.ndarray) -> dict:
         """Word_Optimization_Analysis (OFDM.c:38-73) of the capture's RRC matched-filter output."""

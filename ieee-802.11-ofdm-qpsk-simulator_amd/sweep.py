@@ -97,6 +97,79 @@ def reference_main(out_dir: str | Path = "data", trials: int = 1, mode: str = "f
     return res
 
 
+def impairment_sweep(engine: Engine, snr_db, cfo_hz, n_trials: int, taps=None, noise: str = "real",
+                     seed: int = 0x80211A, payload: str = "message", mode: str = "c",
+                     budget_bytes: int = 256 << 20) -> np.ndarray:
+    """BER / EVM / sync counters against carrier frequency offset and SNR in the reference's own trial, sync and CFO
+    estimation included: counters[n_cfo][n_snr][NCOUNTERS].  Every point runs n_trials captures through
+    channel.make_captures (capture starts and noise from one torch generator seeded with `seed`) and
+    Engine.receive_captures, in chunks whose captures stay below budget_bytes.  Single context: the counters are sums,
+    so trials can be sharded over GPUs and added (dist.py)."""
+    import torch  # noqa: PLC0415
+    from .channel import make_captures  # noqa: PLC0415
+    snr = np.atleast_1d(np.asarray(snr_db, np.float64))
+    cfo = np.atleast_1d(np.asarray(cfo_hz, np.float64))
+    dev = torch.device("cuda", engine.device)
+    opts = abi.make_rx_opts(mode)
+    L = opts.cap_len or abi.capture_len(engine.payload_frames(payload))
+    wave = torch.from_numpy(engine.transmitter("c" if mode == "c" else "matlab", payload)).to(dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    chunk = max(1, int(budget_bytes) // (8 * L))
+    out = torch.zeros((len(cfo), len(snr), abi.NCOUNTERS), dtype=torch.int64, device=dev)
+    for ci, f in enumerate(cfo):
+        for si, s in enumerate(snr):
+            done = 0
+            while done < n_trials:
+                m = min(chunk, n_trials - done)
+                starts = torch.randint(0, wave.shape[0] - L, (m,), generator=gen, device=dev)   # OFDM.c:949
+                caps = make_captures(wave, starts, float(s), float(f), taps=taps, noise=noise, generator=gen, cap_len=L)
+                engine.receive_captures(caps, mode=mode, payload=payload, want_bits=False, counters=out[ci, si])
+                done += m
+    return out.cpu().numpy()
+
+
+def captures_main(argv=None):
+    """`ofdm_pkg.py captures`: the reference's four Output_*.txt files per CFO value, from impairment_sweep."""
+    from .channel import NOISE_KINDS, parse_taps  # noqa: PLC0415
+    ap = argparse.ArgumentParser(description="BER / EVM against SNR under CFO, multipath and complex noise "
+                                             "(batched receiver for caller-supplied captures)")
+    ap.add_argument("--out", default="data")
+    ap.add_argument("--trials", type=int, default=100, help="captures per (CFO, SNR) point")
+    ap.add_argument("--snr", type=float, nargs="*", help="SNR grid in dB (default 6..40 step 1)")
+    ap.add_argument("--cfo-hz", type=float, action="append", help="carrier frequency offset in Hz (repeatable; default 0)")
+    ap.add_argument("--taps", help="multipath FIR at the oversampled rate, e.g. 1,0,0.4+0.3j")
+    ap.add_argument("--noise", choices=list(NOISE_KINDS), default="real")
+    ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x80211A)
+    ap.add_argument("--message", help="MESSAGE payload text (default: OFDM.c:20), up to 180 characters")
+    a = ap.parse_args(argv)
+    snr = np.array(a.snr) if a.snr else REF_SNR
+    cfo = a.cfo_hz or [0.0]
+    taps = parse_taps(a.taps) if a.taps else None
+    out = Path(a.out)
+    if not out.is_dir():
+        raise FileNotFoundError(f"output directory {out} does not exist")
+    t0 = time.perf_counter()
+    with Engine(0) as eng:
+        if a.message is not None:
+            set_message(eng, a.message)
+        c = impairment_sweep(eng, snr, cfo, a.trials, taps=taps, noise=a.noise, seed=a.seed)
+    wall = time.perf_counter() - t0
+    side = {"trials_per_point": a.trials, "seed": a.seed, "noise": a.noise, "wall_s": wall,
+            "taps": None if taps is None else [[float(t.real), float(t.imag)] for t in taps],
+            "snr_db": snr.tolist(), "cfo_hz": [float(f) for f in cfo], "counters": c.tolist(), "dirs": []}
+    for ci, f in enumerate(cfo):
+        res = SweepResult(snr, c[ci])
+        d = out if len(cfo) == 1 else out / f"cfo_{f:g}"
+        d.mkdir(exist_ok=True)
+        write_reference_outputs(d, res.snr_db, res.mean_frame_evm_db, res.mean_frame_evm_post_db, res.ber)
+        side["dirs"].append(str(d))
+        for s, b, sf in zip(res.snr_db, res.ber, res.sync_fail_rate):
+            print(f"CFO = {f:9.1f} Hz   SNR = {s:5.1f} dB   BER = {b:.3e}   sync fail = {sf:.3f}", file=sys.stderr)
+    (out / "ofdm_captures.json").write_text(json.dumps(side, indent=1))
+    return c
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="802.11a OFDM-QPSK Monte-Carlo sweep on MI355X (OFDM.c main())")
     ap.add_argument("--out", default="data")
