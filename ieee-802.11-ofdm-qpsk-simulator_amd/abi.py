@@ -31,6 +31,7 @@ EVM_Q_SCALE = float(1 << 20)
 
 # kernel ids for timing
 K_FFT, K_TX, K_RX, K_FRAME = range(4)
+K_STREAM_DETECT, K_STREAM_SELECT, K_STREAM_DECODE = 4, 5, 6     # OFDM_K_STREAM_* (ofdm_mi355x_stream.h)
 
 # every entry point of the header, with ctypes argument types
 _V = C.c_void_p
@@ -86,6 +87,16 @@ CAPTURES_EXPORTS = tuple(_CAPTURES_SIGS)
 CAPTURE_MAX_LEN = 9400             # OFDM_CAPTURE_MAX_LEN
 CAPTURE_SYNC_FAIL, CAPTURE_OOB = 1, 2      # ofdm_capture_result.flags
 
+# the extension header include/ofdm_mi355x_stream.h (detection once over one recording of any length, every packet
+# decoded); the export lists above and ABI_VERSION do not change with it
+STREAM_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_stream.h"
+_STREAM_SIGS = {
+    "ofdm_receive_stream": (C.c_int, [_V, _V, C.c_int64, _V, C.c_int, C.c_int64, _V, _V, _V, _V, _V, _V, _V]),
+}
+STREAM_EXPORTS = tuple(_STREAM_SIGS)
+STREAM_LAST_FRONT = 4              # OFDM_STREAM_LAST_FRONT, ofdm_capture_result.flags bit 2
+STREAM_RUN, STREAM_TILE = 31, 7936  # OFDM_STREAM_RUN, OFDM_STREAM_TILE
+
 
 class OfdmError(RuntimeError):
     pass
@@ -118,6 +129,17 @@ def capture_result_dtype():
     return np.dtype([("packet_idx", "<i4"), ("flags", "<i4"), ("bit_err", "<i4"), ("post_axis_err", "<i4"),
                      ("evm_pre_sum", "<f4"), ("evm_db_pre", "<f4"), ("evm_db_post", "<f4"), ("ber", "<f4"),
                      ("cfo_coarse_hz", "<f4"), ("cfo_fine_hz", "<f4"), ("reserved", "<i4", (2,))])
+
+
+class StreamPacket(C.Structure):
+    """ofdm_stream_packet (64 bytes, one per packet)"""
+    _fields_ = [("packet_pos", C.c_int64), ("reserved", C.c_int64), ("r", CaptureResult)]
+
+
+def stream_packet_dtype():
+    """numpy structured dtype of ofdm_stream_packet: packet_pos, reserved, then ofdm_capture_result's fields flat"""
+    import numpy as np  # noqa: PLC0415
+    return np.dtype([("packet_pos", "<i8"), ("reserved8", "<i8")] + capture_result_dtype().descr)
 
 
 def reduce_capture_records(rec, frames: int):
@@ -194,7 +216,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
         raise OfdmError(f"{p} not found: the HIP library must be built (build_lib.build()); "
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS}.items():
+    for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -75,9 +75,63 @@ def make_captures(wave, starts, snr_db, cfo_hz=0.0, taps=None, noise: str = "rea
     return caps.contiguous()
 
 
+def make_stream(wave, segments, snr_db, cfo_hz=0.0, taps=None, noise: str = "real", generator=None):
+    """One recording (complex64 [n], on wave's device) for Engine.receive_stream: idle gaps and slices of the repeated
+    waveform `wave` (complex64 [len]) laid end to end, then make_captures' impairments 1 to 3 over the whole of it.
+
+    segments: a sequence of ("gap", n) -- n zero samples -- and ("wave", lo, hi) -- samples [lo, hi) of the waveform
+    repeated without end (index modulo its length), 0 <= lo <= hi.  The multipath FIR runs over the laid-out stream
+    truncated to its length, the rotation exp(j 2 pi cfo_hz k 25e-9) goes by the stream index k, and the noise (power
+    mean|wave|^2 / 10^(snr_db / 10), measured on `wave`) covers gaps and packets alike.  snr_db and cfo_hz are
+    scalars.  A stream that is one whole `wave` equals make_captures(wave, 0, ..., cap_len=len(wave))[0], noise
+    included when the generators start alike."""
+    torch = _torch()
+    if noise not in NOISE_KINDS:
+        raise ValueError(f"noise must be one of {NOISE_KINDS}, got {noise!r}")
+    wave = torch.as_tensor(wave)
+    if wave.dim() != 1 or not wave.is_complex() or wave.shape[0] == 0:
+        raise ValueError("wave must be a non-empty one-dimensional complex tensor")
+    wave = wave.to(torch.complex64)
+    dev, wl = wave.device, int(wave.shape[0])
+    parts = []
+    for seg in segments:
+        kind = seg[0] if len(seg) else None
+        if kind == "gap" and len(seg) == 2 and int(seg[1]) >= 0:
+            parts.append(torch.zeros(int(seg[1]), dtype=torch.complex64, device=dev))
+        elif kind == "wave" and len(seg) == 3 and 0 <= int(seg[1]) <= int(seg[2]):
+            parts.append(wave[torch.arange(int(seg[1]), int(seg[2]), device=dev, dtype=torch.int64) % wl])
+        else:
+            raise ValueError(f"a segment is ('gap', n >= 0) or ('wave', lo, hi) with 0 <= lo <= hi, got {seg!r}")
+    x = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.complex64, device=dev)
+    n = int(x.shape[0])
+    power = float(torch.mean(wave.real.double() ** 2 + wave.imag.double() ** 2))        # OFDM.c:637-643
+    y = x
+    if taps is not None:
+        h = np.asarray(taps, np.complex64).ravel()
+        y = torch.zeros_like(x)
+        for j, hj in enumerate(h):
+            if hj != 0 and j < n:
+                y[j:] += complex(hj) * x[:n - j]
+    if float(cfo_hz) != 0.0:
+        k = torch.arange(n, device=dev, dtype=torch.int64)
+        rev = float(cfo_hz) * k.double() * TS_OVERSAMPLED
+        ang = (2.0 * np.pi) * (rev - torch.round(rev))
+        y = y * torch.complex(torch.cos(ang), torch.sin(ang)).to(torch.complex64)
+    if noise != "none":
+        sigma = torch.sqrt(torch.as_tensor(power / 10.0 ** (float(snr_db) / 10.0), dtype=torch.float64, device=dev)).float()
+        if noise == "real":
+            g = torch.randn((1, n), generator=generator, device=dev, dtype=torch.float32)[0]
+            nz = torch.complex(g * sigma, torch.zeros_like(g))
+        else:
+            g = torch.randn((1, n, 2), generator=generator, device=dev, dtype=torch.float32)[0]
+            nz = torch.view_as_complex((g * (sigma * (0.5 ** 0.5))).contiguous())
+        y = y + nz
+    return y.contiguous()
+
+
 def parse_taps(text: str) -> np.ndarray:
     """'1,0,0.4+0.3j' -> complex64 taps"""
     return np.array([complex(t.strip()) for t in text.split(",") if t.strip()], np.complex64)
 
 
-__all__ = ["make_captures", "parse_taps", "TS_OVERSAMPLED"]
+__all__ = ["make_captures", "make_stream", "parse_taps", "TS_OVERSAMPLED"]

@@ -29,7 +29,8 @@ struct Ctx;
 int check_symbol_payload(const Ctx *c, int payload);
 
 struct Ctx {
-    enum { K_FFT = 0, K_TX = 1, K_RX = 2, K_FRAME = 3, NK = 4 };
+    // 4..6: the stream receiver's kernels (OFDM_K_STREAM_* of ofdm_mi355x_stream.h), added at the tail
+    enum { K_FFT = 0, K_TX = 1, K_RX = 2, K_FRAME = 3, K_STREAM_DETECT = 4, K_STREAM_SELECT = 5, K_STREAM_DECODE = 6, NK = 7 };
     int device = 0;
     int cus = 256;
     hipStream_t own = nullptr;       // created by the context
@@ -67,8 +68,8 @@ struct Ctx {
     bool timing = false;
     std::vector<Ev> open, done;
     std::vector<hipEvent_t> pool;
-    double acc_ms[NK] = {0, 0, 0, 0};
-    int64_t launches[NK] = {0, 0, 0, 0};
+    double acc_ms[NK] = {};
+    int64_t launches[NK] = {};
 
     void tic(int k);
     void toc();

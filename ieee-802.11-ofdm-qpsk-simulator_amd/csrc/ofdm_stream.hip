@@ -1,0 +1,678 @@
+// ofdm_stream.hip -- the stream receiver (include/ofdm_mi355x_stream.h: ofdm_receive_stream): Packet_Detection and
+// Packet_Selection (OFDM.c:659-771) once over one device-resident recording of any length, then Receiver()'s chain
+// (OFDM.c:962-1165) on every packet found.  A translation unit of its own: ofdm_captures.hip (one capture per wave,
+// at most one packet per capture) is certified as it is, so nothing of it moves; this file shares only the inlined
+// device helpers of ofdm_rxcommon.h with it and restates capture_rx_kernel's post-selection chain (see
+// stream_decode_kernel).
+//
+//   stream_detect_kernel<METRIC> : a block takes OFDM_STREAM_TILE positions.  It stages TILE + 47 samples once
+//     (16-byte loads, real and imaginary planes in LDS; the 47-sample halo is the only re-read), a lane owns one run
+//     of OFDM_STREAM_RUN contiguous positions (odd: the lanes' strides fall on distinct banks), opens it with the
+//     direct 32-term sum and slides in fp32 as capture_rx_kernel does.  RUN BOUNDARIES ARE FIXED IN ABSOLUTE STREAM
+//     COORDINATES -- run j is [j RUN, (j + 1) RUN), tile t is runs [256 t, 256 (t + 1)) -- so every M[i] and every
+//     crossing is bit-identical whatever the grid, the tile-to-block assignment or the alignment of the samples.
+//     Crossings are gathered in an LDS bitmap and leave as whole 32-bit words, 16 bytes per lane.
+//   stream_select_kernel<PHASE> : integer logic on the bitmap alone.  0: a thread owns one slot of 301 positions (at
+//     most one front: fronts are more than 300 apart), finds the slot's front (a set bit whose predecessor is clear,
+//     at position >= 300 -- the virtual crossing at -1 -- with 300 clear bits behind it, read from the neighbouring
+//     words in global memory) and its +230 confirmation; per block the number of confirmed fronts and the largest
+//     front.  1: one block scans the blocks' counts in order, reduces the largest front and writes d_count.
+//     2: ordered compaction -- slot order is position order -- of the first max_packets confirmed fronts into
+//     packet_pos, with the LAST_FRONT flag.  No arrival-order append anywhere: the output is deterministic.
+//   stream_decode_kernel<OUT> : one wave per packet, W waves per block, looping over d_count.  A wave stages only
+//     [p - 20, p + 2 nfr - 2] (2 nfr + 19 samples, zero outside the stream) and runs capture_rx_kernel's chain on it.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include "ofdm_mi355x_stream.h"
+#include "ofdm_ctx.h"
+#include "ofdm_rxcommon.h"
+
+namespace ofdm {
+
+constexpr int SD_RUN = OFDM_STREAM_RUN;
+constexpr int SD_THREADS = 256;
+constexpr int SD_TILE = OFDM_STREAM_TILE;
+constexpr int SD_SAMPLES = SD_TILE + 47;
+constexpr int SD_PLANE = (SD_SAMPLES + 3) & ~3;
+constexpr int SD_WORDS = SD_TILE / 32;
+constexpr int SD_LOADS = (SD_SAMPLES / 2 + SD_THREADS - 1) / SD_THREADS;      // 16-byte loads per lane and tile
+static_assert(SD_TILE == SD_RUN * SD_THREADS && SD_TILE % 128 == 0 && (SD_RUN & 1), "tile = 256 odd runs, whole 16-byte groups of bitmap words");
+static_assert(SD_RUN <= 147, "no run longer than capture_rx_kernel's longest (the measured fp32 drift is the precedent)");
+static_assert((2 * SD_PLANE + SD_WORDS) * 4 <= 64 * 1024, "static LDS");
+constexpr int SS_THREADS = 256;           // slots per block of the selection kernel
+constexpr int SS_SLOT = 301;              // positions per slot: fronts are at least 301 apart
+constexpr int SS_SCAN_THREADS = 1024;
+
+constexpr int SDEC_MAX_DATA = LONG_MAX_FRAMES;
+constexpr int SDEC_MAX_WAVES = 8;                     // 512 threads: two waves per SIMD, 256 VGPRs each
+constexpr size_t SDEC_LDS_PER_CU = 160 * 1024;
+constexpr int SDEC_ACC_WORDS = OFDM_NCOUNTERS;
+constexpr double SDEC_TS = 1.0 / 20e6;                // OFDM.c:16-17
+constexpr int SDEC_SPEC_PITCH = 130;                  // floats per parked spectrum (as capture_rx_kernel)
+constexpr int SDEC_LOADS = 8;                         // 16-byte loads a lane keeps in flight while staging (all of a 2-symbol packet's)
+constexpr uint64_t sdec_ltf_neg() {
+    uint64_t v = 0;
+    for (int b = 0; b < 64; ++b) v |= (uint64_t)(ltf_sign(b) < 0) << b;
+    return v;
+}
+constexpr uint64_t SDEC_LTF_NEG = sdec_ltf_neg();
+static_assert(sizeof(ofdm_stream_packet) == 64, "ofdm_stream_packet is 64 bytes");
+
+struct DetArgs {
+    const float2 *x;
+    int64_t n, lc, tiles, words;   // samples, positions, tiles, bitmap words
+    uint32_t *bitmap;              // scratch, padded to whole 16-byte groups
+    uint32_t *cross;               // the caller's copy (optional)
+    float *metric;                 // optional
+};
+
+template <bool METRIC>
+__global__ __launch_bounds__(SD_THREADS) void stream_detect_kernel(DetArgs a) {
+    __shared__ __attribute__((aligned(16))) float re[SD_PLANE];
+    __shared__ __attribute__((aligned(16))) float im[SD_PLANE];
+    __shared__ __attribute__((aligned(16))) uint32_t bm[SD_WORDS];
+    const int tid = threadIdx.x;
+    // 1: the stream starts 8 bytes off a 16-byte line; tiles start at even samples, so every tile shares it
+    const int head = (int)((reinterpret_cast<uintptr_t>(a.x) >> 3) & 1u);
+    for (int64_t t = blockIdx.x; t < a.tiles; t += gridDim.x) {
+        const int64_t t0 = t * SD_TILE;
+        // ---- stage [t0, t0 + TILE + 47) clipped to the stream; the rest of the planes and the bitmap zeroed ----
+        {
+            const float2 *row = a.x + t0;
+            const int cnt = (int)std::min<int64_t>(SD_SAMPLES, a.n - t0);
+            if (head && tid == 0) { const float2 v = row[0]; re[0] = v.x; im[0] = v.y; }
+            const f4v *r4 = reinterpret_cast<const f4v *>(row + head);
+            const int np = (cnt - head) >> 1;
+            // every load of the tile is in flight before the first LDS write (issued one after the other, each behind
+            // the LDS writes of the one before, the kernel measured 1.00 ms on a 2^28-sample stream against 0.71 ms)
+            f4v v[SD_LOADS];
+#pragma unroll
+            for (int j = 0; j < SD_LOADS; ++j) {
+                const int k = tid + j * SD_THREADS;
+                if (k < np) v[j] = __builtin_nontemporal_load(r4 + k);
+            }
+#pragma unroll
+            for (int j = 0; j < SD_LOADS; ++j) {
+                const int k = tid + j * SD_THREADS;
+                if (k >= np) continue;
+                if (head) {
+                    const int m = 1 + 2 * k;
+                    re[m] = v[j].x; im[m] = v[j].y; re[m + 1] = v[j].z; im[m + 1] = v[j].w;
+                } else {
+                    *reinterpret_cast<float2 *>(re + 2 * k) = make_float2(v[j].x, v[j].z);
+                    *reinterpret_cast<float2 *>(im + 2 * k) = make_float2(v[j].y, v[j].w);
+                }
+            }
+            if (((cnt - head) & 1) && tid == 0) { const float2 v = row[cnt - 1]; re[cnt - 1] = v.x; im[cnt - 1] = v.y; }
+            for (int k = cnt + tid; k < SD_PLANE; k += SD_THREADS) { re[k] = 0.f; im[k] = 0.f; }
+            if (tid < SD_WORDS) bm[tid] = 0u;
+        }
+        __syncthreads();
+        // ---- this lane's run: positions t0 + [n0, n0 + cnt) ----
+        {
+            const int n0 = tid * SD_RUN;
+            const int cnt = (int)std::min<int64_t>(SD_RUN, a.lc - (t0 + n0));
+            if (cnt > 0) {
+                float sx = 0.f, sy = 0.f, pw = 0.f;
+                int nz = 0;                                            // samples of the power window that are not zero
+#pragma unroll 8
+                for (int k = 0; k < 32; ++k) {
+                    const float ux = re[n0 + k], uy = im[n0 + k], vx = re[n0 + k + 16], vy = im[n0 + k + 16];
+                    sx = fmaf(ux, vx, sx); sx = fmaf(-uy, vy, sx);
+                    sy = fmaf(ux, vy, sy); sy = fmaf(uy, vx, sy);
+                    pw = fmaf(vx, vx, pw); pw = fmaf(vy, vy, pw);
+                    nz += (vx != 0.f) | (vy != 0.f);
+                }
+                for (int j = 0; j < cnt; ++j) {
+                    const int n = n0 + j;
+                    // an all-zero power window has c = p = 0 exactly: what the slide left behind is rounding residue of
+                    // the samples that have gone, and must not decide a crossing (idle gaps have none)
+                    if (nz == 0) { sx = 0.f; sy = 0.f; pw = 0.f; }
+                    const float num = fmaf(sx, sx, sy * sy), h = 0.75f * pw;
+                    if (fmaf(h, pw, -num) < 0.f) atomicOr(&bm[n >> 5], 1u << (n & 31));     // |c|^2 / p^2 > 0.75
+                    if constexpr (METRIC) a.metric[t0 + n] = num / (pw * pw);
+                    if (j + 1 < cnt) {                                 // n + 48 <= t0 + n0 + cnt + 46 < the stream's end
+                        const float o0x = re[n], o0y = im[n], o1x = re[n + 16], o1y = im[n + 16];
+                        const float i0x = re[n + 32], i0y = im[n + 32], i1x = re[n + 48], i1y = im[n + 48];
+                        sx = fmaf(i0x, i1x, sx); sx = fmaf(-i0y, i1y, sx);
+                        sx = fmaf(-o0x, o1x, sx); sx = fmaf(o0y, o1y, sx);
+                        sy = fmaf(i0x, i1y, sy); sy = fmaf(i0y, i1x, sy);
+                        sy = fmaf(-o0x, o1y, sy); sy = fmaf(-o0y, o1x, sy);
+                        pw = fmaf(i1x, i1x, pw); pw = fmaf(i1y, i1y, pw);
+                        pw = fmaf(-o1x, o1x, pw); pw = fmaf(-o1y, o1y, pw);
+                        nz += (int)((i1x != 0.f) | (i1y != 0.f)) - (int)((o1x != 0.f) | (o1y != 0.f));
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // ---- the tile's bitmap words: 16 bytes per lane into the scratch bitmap, and the caller's copy ----
+        {
+            const int64_t w0 = t0 >> 5;
+            if (tid < SD_WORDS / 4 && w0 + 4 * tid < a.words)          // the scratch bitmap is padded to whole groups
+                reinterpret_cast<uint4 *>(a.bitmap + w0)[tid] = reinterpret_cast<const uint4 *>(bm)[tid];
+            if (a.cross && tid < SD_WORDS && w0 + tid < a.words) a.cross[w0 + tid] = bm[tid];
+        }
+        __syncthreads();                                               // the next tile overwrites the planes
+    }
+}
+
+struct SelArgs {
+    const uint32_t *bitmap;
+    int64_t lc, nslots, nblocks, max_packets;
+    int64_t *slots;        // [nslots] front << 1 | confirmed, or -1
+    int64_t *blk_cnt;      // [nblocks] confirmed fronts of the block; after phase 1 their exclusive prefix
+    int64_t *blk_max;      // [nblocks] largest front of the block, -1 when none; after phase 1 [0] the stream's
+    int64_t *count;        // d_count
+    ofdm_stream_packet *pk;
+};
+
+// bits [lo, hi) of the bitmap are all clear (0 <= lo < hi)
+__device__ __forceinline__ bool stream_bits_clear(const uint32_t *bm, int64_t lo, int64_t hi) {
+    for (int64_t w = (hi - 1) >> 5; w >= (lo >> 5); --w) {
+        uint32_t x = bm[w];
+        const int64_t base = w << 5;
+        if (base < lo) x &= ~0u << (int)(lo - base);
+        if (base + 32 > hi) x &= ~0u >> (int)(base + 32 - hi);
+        if (x) return false;
+    }
+    return true;
+}
+
+// block-wide sum and maximum of 64-bit values (SS_THREADS threads; red has 2 x 4 words)
+__device__ __forceinline__ void stream_block_reduce(int64_t cnt, int64_t mx, int64_t *red, int64_t &cnt_out, int64_t &mx_out) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        cnt += __shfl_xor(cnt, o, 64);
+        mx = max(mx, (int64_t)__shfl_xor(mx, o, 64));
+    }
+    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { red[wave] = cnt; red[16 + wave] = mx; }
+    __syncthreads();
+    cnt_out = 0;
+    mx_out = -1;
+    for (int k = 0; k < nw; ++k) { cnt_out += red[k]; mx_out = max(mx_out, red[16 + k]); }
+}
+
+template <int PHASE>
+__global__ __launch_bounds__(PHASE == 1 ? SS_SCAN_THREADS : SS_THREADS) void stream_select_kernel(SelArgs a) {
+    __shared__ int64_t red[32];
+    if constexpr (PHASE == 0) {
+        const int64_t s = (int64_t)blockIdx.x * SS_THREADS + threadIdx.x;
+        int64_t front = -1;
+        bool conf = false;
+        if (s < a.nslots) {
+            const int64_t lo = s * SS_SLOT, hi = min(lo + SS_SLOT, a.lc);
+            for (int64_t w = lo >> 5; w <= ((hi - 1) >> 5) && front < 0; ++w) {
+                const uint32_t x = a.bitmap[w];
+                const uint32_t prev = w > 0 ? a.bitmap[w - 1] >> 31 : 0u;
+                uint32_t cand = x & ~((x << 1) | prev);                 // set bits whose predecessor is clear
+                const int64_t base = w << 5;
+                if (base < lo) cand &= ~0u << (int)(lo - base);
+                if (base + 32 > hi) cand &= ~0u >> (int)(base + 32 - hi);
+                while (cand) {
+                    const int64_t i = base + (__ffs((int)cand) - 1);
+                    cand &= cand - 1;
+                    // previous crossing more than 300 back; none at all is the virtual crossing at -1
+                    if (i >= 300 && stream_bits_clear(a.bitmap, i - 300, i)) { front = i; break; }
+                }
+            }
+            if (front >= 0) {
+                const int64_t j = front + 230;
+                conf = j < a.lc && ((a.bitmap[j >> 5] >> (int)(j & 31)) & 1u);
+            }
+            a.slots[s] = front < 0 ? -1 : (front << 1) | (int64_t)conf;
+        }
+        int64_t c, m;
+        stream_block_reduce((int64_t)conf, front, red, c, m);
+        if (threadIdx.x == 0) { a.blk_cnt[blockIdx.x] = c; a.blk_max[blockIdx.x] = m; }
+    } else if constexpr (PHASE == 1) {
+        // one block: exclusive prefix of the blocks' counts in block order, the largest front, d_count
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        int64_t carry = 0, mx = -1;
+        for (int64_t b0 = 0; b0 < a.nblocks; b0 += SS_SCAN_THREADS) {
+            const int64_t b = b0 + threadIdx.x;
+            const int64_t v = b < a.nblocks ? a.blk_cnt[b] : 0;
+            if (b < a.nblocks) mx = max(mx, a.blk_max[b]);
+            int64_t inc = v;                                            // inclusive scan inside the wave
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int64_t u = __shfl_up(inc, o, 64);
+                inc += lane >= o ? u : 0;
+            }
+            __syncthreads();
+            if (lane == 63) red[wave] = inc;
+            __syncthreads();
+            int64_t before = 0, total = 0;
+            for (int k = 0; k < SS_SCAN_THREADS / 64; ++k) { before += k < wave ? red[k] : 0; total += red[k]; }
+            if (b < a.nblocks) a.blk_cnt[b] = carry + before + inc - v;
+            carry += total;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mx = max(mx, (int64_t)__shfl_xor(mx, o, 64));
+        __syncthreads();
+        if (lane == 0) red[16 + wave] = mx;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int k = 0; k < SS_SCAN_THREADS / 64; ++k) mx = max(mx, red[16 + k]);
+            a.blk_max[0] = mx;
+            a.count[0] = carry;
+            a.count[1] = min(carry, a.max_packets);
+        }
+    } else {
+        // ordered compaction: slot order is position order
+        const int64_t s = (int64_t)blockIdx.x * SS_THREADS + threadIdx.x;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int64_t v = s < a.nslots ? a.slots[s] : -1;
+        const bool conf = v >= 0 && (v & 1);
+        const unsigned long long bal = __ballot(conf);
+        if (lane == 0) red[wave] = __popcll(bal);
+        __syncthreads();
+        int64_t idx = a.blk_cnt[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
+        for (int k = 0; k < wave; ++k) idx += red[k];
+        if (conf && idx < a.max_packets) {
+            const int64_t front = v >> 1, p = front + 11;              // len_RRC_rx + 1 (OFDM.c:758)
+            ofdm_stream_packet *q = a.pk + idx;
+            q->packet_pos = p;
+            q->reserved = 0;
+            q->r.flags = front == a.blk_max[0] ? OFDM_STREAM_LAST_FRONT : 0;   // the decode kernel adds the oob bit
+        }
+    }
+}
+
+struct DecArgs {
+    const float2 *x;
+    int64_t n;
+    const int64_t *count;    // d_count: [1] records to decode
+    ofdm_stream_packet *pk;
+    uint32_t *bits;
+    float2 *eq;
+    unsigned long long *counters;
+    int32_t n_data, float_cfo;
+    int32_t plane;           // floats per plane (2 nfr + 19 rounded up to 4)
+    int32_t wave_floats;     // floats per wave: two planes and fr[]
+    float taps[21];
+    uint32_t dtable[4 * SDEC_MAX_DATA];
+};
+
+// LDS ordering between the lanes of one wave (the block's other waves run other packets)
+__device__ __forceinline__ void sdec_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ float sdec_sum_f(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// rotate by exp(-j 2 pi f Ts i): the phase in revolutions in fp64, range-reduced, then v_sin / v_cos (OFDM.c:802,825)
+__device__ __forceinline__ float2 sdec_rot(float2 v, double f_ts, int i) {
+    const double rev = -f_ts * (double)i;
+    const float fr = (float)(rev - rint(rev));
+    const float s = __builtin_amdgcn_sinf(fr), c = __builtin_amdgcn_cosf(fr);
+    return make_float2(v.x * c - v.y * s, v.x * s + v.y * c);
+}
+// frame sample ii is one the receiver uses: STF tail [80, 112), LTF pair [192, 320), data symbols past their prefixes
+__device__ __forceinline__ bool sdec_needed(int ii) {
+    if (ii < 192) return ii >= 80 && ii < 112;
+    if (ii < 320) return true;
+    const int r = (ii - 320) % 80;
+    return r >= 16;
+}
+
+// capture_rx_kernel's chain from the matched filter on (ofdm_captures.hip), restated here so that that kernel's
+// certified build does not move: the same filter tap order, atan2_cfo, rotation, quads, park-and-second-pass outputs
+// and counter terms, so a packet's record is what capture_rx_kernel gives for a window that contains it.  What
+// differs is the staging: the wave holds only the samples the filter reads, sample s of the stream at plane index
+// s - (p - 20), zero outside the stream, so the filter needs no bounds test.
+template <bool OUT>   // OUT: d_bits and / or d_eq are written
+__global__ __launch_bounds__(64 * SDEC_MAX_WAVES) void stream_decode_kernel(DecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sdec_smem[];
+    unsigned long long *acc = sdec_smem;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), W = blockDim.x >> 6;
+    const int nd = a.n_data, nfr = 320 + 80 * nd, plane = a.plane, len = 2 * nfr + 19;
+    float *re = reinterpret_cast<float *>(sdec_smem + SDEC_ACC_WORDS) + (size_t)wave * a.wave_floats;
+    float *im = re + plane;
+    float *fre = re + 2 * plane, *fim = fre + nfr;
+    if (threadIdx.x < SDEC_ACC_WORDS) acc[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t cnt = a.count[1];
+    const int q = (int)((reinterpret_cast<uintptr_t>(a.x) >> 3) & 1u);     // sample s is 16-byte aligned when s + q is even
+    for (int64_t i = (int64_t)blockIdx.x * W + wave; i < cnt; i += (int64_t)gridDim.x * W) {
+        ofdm_stream_packet *pkt = a.pk + i;
+        const int64_t pv = pkt->packet_pos;
+        const int64_t p = ((int64_t)__builtin_amdgcn_readfirstlane((int)(pv >> 32)) << 32) |
+                          (uint32_t)__builtin_amdgcn_readfirstlane((int)pv);
+        const int last_front = __builtin_amdgcn_readfirstlane(pkt->r.flags) & OFDM_STREAM_LAST_FRONT;
+        // ---- stage [p - 20, p + 2 nfr - 2]: aligned 16-byte loads inside the stream, zero outside ----
+        {
+            const int64_t s0 = p - 20, e0 = s0 - ((s0 + q) & 1);
+            for (int kb = lane; 2 * kb < len + 1; kb += 64 * SDEC_LOADS) {     // SDEC_LOADS loads in flight, then their writes
+                f4v t[SDEC_LOADS];
+#pragma unroll
+                for (int j = 0; j < SDEC_LOADS; ++j) {
+                    const int k = kb + 64 * j;
+                    const int64_t s = e0 + 2 * k;
+                    t[j] = f4v{0.f, 0.f, 0.f, 0.f};
+                    if (2 * k >= len + 1) continue;
+                    if (s >= 0 && s + 1 < a.n) {
+                        t[j] = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(a.x + s));
+                    } else {
+                        if (s >= 0 && s < a.n) { const float2 u = a.x[s]; t[j].x = u.x; t[j].y = u.y; }
+                        if (s + 1 >= 0 && s + 1 < a.n) { const float2 u = a.x[s + 1]; t[j].z = u.x; t[j].w = u.y; }
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < SDEC_LOADS; ++j) {
+                    const int k = kb + 64 * j;
+                    const int m = 2 * k - (int)(s0 - e0);                  // -1 for the pair's first sample when e0 < s0
+                    if (2 * k >= len + 1) continue;
+                    if (m >= 0 && m < len) { re[m] = t[j].x; im[m] = t[j].y; }
+                    if (m + 1 < len) { re[m + 1] = t[j].z; im[m + 1] = t[j].w; }
+                }
+            }
+        }
+        sdec_wave_sync();
+        // ---- RRC matched filter at the down-sampled instants: stream sample p + 2 ii - tt is plane index 20 + 2 ii - tt ----
+        const bool oob = p + 2 * (int64_t)(nfr - 1) >= a.n + 20;       // the reference reads past its buffer
+        for (int ii = lane; ii < nfr; ii += 64) {
+            if (!sdec_needed(ii)) continue;
+            const int n = 20 + 2 * ii;
+            float vx = 0.f, vy = 0.f;
+#pragma unroll
+            for (int tt = 0; tt < 21; ++tt) {
+                vx = fmaf(re[n - tt], a.taps[tt], vx);
+                vy = fmaf(im[n - tt], a.taps[tt], vy);
+            }
+            fre[ii] = vx;
+            fim[ii] = vy;
+        }
+        sdec_wave_sync();
+        // ---- Coarse_CFO_Estimation, Fine_CFO_Estimation (OFDM.c:773-828) ----
+        double fc, ff;
+        {
+            const int k = lane & 15;
+            const float2 cu = make_float2(fre[80 + k], fim[80 + k]), cw = make_float2(fre[96 + k], fim[96 + k]);
+            float2 pp = lane < 16 ? cmulc(cu, cw) : make_float2(0.f, 0.f);
+            pp.x = sdec_sum_f(pp.x);
+            pp.y = sdec_sum_f(pp.y);
+            fc = (-1.0 / (2.0 * M_PI * 16.0 * SDEC_TS)) * (double)atan2_cfo(pp.y, pp.x);
+            if (a.float_cfo) fc = (double)(float)fc;
+            const float2 u = sdec_rot(make_float2(fre[192 + lane], fim[192 + lane]), fc * SDEC_TS, 192 + lane);
+            const float2 w = sdec_rot(make_float2(fre[256 + lane], fim[256 + lane]), fc * SDEC_TS, 256 + lane);
+            pp = cmulc(u, w);
+            pp.x = sdec_sum_f(pp.x);
+            pp.y = sdec_sum_f(pp.y);
+            ff = (-1.0 / (2.0 * M_PI * 64.0 * SDEC_TS)) * (double)atan2_cfo(pp.y, pp.x);
+            if (a.float_cfo) ff = (double)(float)ff;
+        }
+        // the sync half of the record and its counter term leave here, so nothing of it stays live over the transforms
+        if (lane == 0) {
+            ofdm_capture_result *r = &pkt->r;
+            r->packet_idx = p <= 0x7fffffffll ? (int32_t)p : -1;
+            r->flags = last_front | (oob ? OFDM_CAPTURE_OOB : 0);
+            r->cfo_coarse_hz = (float)fc;
+            r->cfo_fine_hz = (float)ff;
+            r->reserved[0] = 0;
+            r->reserved[1] = 0;
+            if (a.counters) atomicAdd(&acc[OFDM_C_OOB], (unsigned long long)oob);
+        }
+        // ---- the combined rotation in place, 64 samples per step: the LTF pair's sum over LTF1, then the data windows ----
+        {
+            const double fcf_ts = (fc + ff) * SDEC_TS;
+            const int k = 192 + lane;
+            const float2 u = sdec_rot(make_float2(fre[k], fim[k]), fcf_ts, k);
+            const float2 w = sdec_rot(make_float2(fre[k + 64], fim[k + 64]), fcf_ts, k + 64);
+            fre[k] = u.x + w.x;
+            fim[k] = u.y + w.y;
+            for (int d = 0; d < nd; ++d) {
+                const int kd = 336 + 80 * d + lane;
+                const float2 v = sdec_rot(make_float2(fre[kd], fim[kd]), fcf_ts, kd);
+                fre[kd] = v.x;
+                fim[kd] = v.y;
+            }
+        }
+        sdec_wave_sync();
+        // ---- symbols: quad {LTF1 + LTF2, D_3q, D_3q+1, D_3q+2}; fft() = DFT(x (-1)^n) ----
+        const int role = lane & 3, dsym = 3 * (lane >> 2) + max(role - 1, 0), dsc = min(dsym, nd - 1);
+        const bool dlane = role >= 1 && dsym < nd;
+        const int k0 = role == 0 ? 192 : 336 + 80 * dsc;
+        float2 x[64];
+        static_for<0, 64>([&](auto nc) {
+            constexpr int n = decltype(nc)::value;
+            const float vx = fre[k0 + n], vy = fim[k0 + n];
+            x[n] = (n & 1) ? make_float2(-vx, -vy) : make_float2(vx, vy);
+        });
+        static_for<0, 16>([&](auto jc) { dif_stage1<false, decltype(jc)::value>(x); });
+        const uint32_t wd[4] = {a.dtable[4 * dsc], a.dtable[4 * dsc + 1], a.dtable[4 * dsc + 2], a.dtable[4 * dsc + 3]};
+        SymState st;
+        sym_init(st);
+        auto Hof = [&](float2 Y, auto binc) { return ls_equalise<decltype(binc)::value>(Y); };
+        // OUT: every window is in registers by now, so the wave's region is free: the quads in use park their finished
+        // spectra there for the output pass below (no branch around the writes: the idle lanes share one more row)
+        [[maybe_unused]] float2 *spec_row = reinterpret_cast<float2 *>(re + min(lane, 4 * ((nd + 2) / 3)) * SDEC_SPEC_PITCH);
+        if constexpr (OUT) sdec_wave_sync();
+        static_for<0, 4>([&](auto rc) {
+            constexpr int R = decltype(rc)::value;
+            dif_sub16<false, R>(x);
+            demap_sub<false, R, 2>(x, wd[R], Hof, nullptr, st);
+            sched_fence();
+            if constexpr (OUT) {
+                static_for<0, 16>([&](auto kc) {
+                    constexpr int bin = 4 * decltype(kc)::value + R;
+                    spec_row[bin] = x[digit_rev4(bin)];
+                });
+                sched_fence();
+            }
+        });
+        // OUT: the equalised subcarriers Z = Y / H = 2 Lf Y conj(S) / |S|^2 and the decided bits (OFDM.c:1044-1052,
+        // 852-908), one subcarrier per lane and step: coalesced stores, a 16-lane OR per word of 32 bits
+        if constexpr (OUT) {
+            sdec_wave_sync();
+            const int nsc = 48 * nd;
+            for (int j0 = 0; j0 < nsc; j0 += 64) {
+                const int j = j0 + lane;
+                const bool ok = j < nsc;
+                const int jj = ok ? j : 0, d = jj / 48, m = jj - 48 * d, bin = data_bin(m);
+                const int l0 = 4 * (d / 3), ln = l0 + 1 + d % 3;
+                const float2 Y = reinterpret_cast<const float2 *>(re + ln * SDEC_SPEC_PITCH)[bin];
+                const float2 S = reinterpret_cast<const float2 *>(re + l0 * SDEC_SPEC_PITCH)[bin];
+                const float r = __builtin_amdgcn_rcpf(fmaf(S.x, S.x, S.y * S.y));
+                const float g = ((SDEC_LTF_NEG >> bin) & 1ull) ? -2.0f * r : 2.0f * r;
+                const float2 u = cmulc(Y, S);
+                const float2 z = make_float2(u.x * g, u.y * g);
+                if (a.eq && ok) a.eq[i * nsc + j] = z;
+                const uint32_t pr = z.x > 0.f, pi = z.y > 0.f;
+                uint32_t wv = ok ? (((pi ^ 1u) << 1) | (pr ^ pi)) << (30 - 2 * (lane & 15)) : 0u;
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) wv |= (uint32_t)__shfl_xor((int)wv, o, 64);
+                if (a.bits && ok && (lane & 15) == 0) a.bits[i * (3 * nd) + (j >> 4)] = wv;
+            }
+        }
+        // ---- the packet's totals in symbol order, its record and its counter terms ----
+        const float fev = dlane ? finish_evm<2>(st) : 0.f;
+        const uint32_t bev = dlane ? st.be : 0u, axv = dlane ? st.ax : 0u;
+        float fe = 0.f;
+        uint32_t ferr = 0u, fax = 0u;
+        for (int d = 0; d < nd; ++d) {
+            const int src = 4 * (d / 3) + 1 + d % 3;
+            fe += __shfl(fev, src, 64);
+            ferr += (uint32_t)__shfl((int)bev, src, 64);
+            fax += (uint32_t)__shfl((int)axv, src, 64);
+        }
+        if (lane == 0) {
+            const float N = 48.0f * (float)nd;
+            const float db = fe > 0.f ? fmaxf(3.01029995663981195214f * __builtin_amdgcn_logf(fe / N), -400.f) : -400.f;
+            const float dbp = fax > 0u ? 3.01029995663981195214f * __builtin_amdgcn_logf(2.0f * (float)fax / N) : -INFINITY;
+            ofdm_capture_result *r = &pkt->r;
+            r->bit_err = (int32_t)ferr;
+            r->post_axis_err = (int32_t)fax;
+            r->evm_pre_sum = fe;
+            r->evm_db_pre = db;
+            r->evm_db_post = dbp;
+            r->ber = (float)ferr / (96.0f * (float)nd);
+            if (a.counters) {
+                const float Q = (float)OFDM_EVM_Q_SCALE;             // x 2^20 is exact in fp32
+                atomicAdd(&acc[OFDM_C_FRAMES], 1ull);
+                atomicAdd(&acc[OFDM_C_SYMBOLS], (unsigned long long)nd);
+                atomicAdd(&acc[OFDM_C_BITS], 96ull * nd);
+                atomicAdd(&acc[OFDM_C_EVM_TERMS], 48ull * nd);
+                atomicAdd(&acc[OFDM_C_BIT_ERR], (unsigned long long)ferr);
+                atomicAdd(&acc[OFDM_C_FRAME_ERR], (unsigned long long)(ferr > 0u));
+                atomicAdd(&acc[OFDM_C_EVM_POST_AXIS], (unsigned long long)fax);
+                atomicAdd(&acc[OFDM_C_EVM_PRE_Q], (unsigned long long)__float2ll_rn(fe * Q));
+                atomicAdd(&acc[OFDM_C_EVMDB_PRE_Q], (unsigned long long)__float2ll_rn(db * Q));
+                if (fax > 0u) {
+                    atomicAdd(&acc[OFDM_C_EVMDB_POST_Q], (unsigned long long)__float2ll_rn(dbp * Q));
+                    atomicAdd(&acc[OFDM_C_EVMDB_POST_FINITE], 1ull);
+                }
+            }
+        }
+        sdec_wave_sync();                                            // the next packet overwrites the planes
+    }
+    __syncthreads();
+    if (a.counters && threadIdx.x < SDEC_ACC_WORDS && acc[threadIdx.x]) atomicAdd(&a.counters[threadIdx.x], acc[threadIdx.x]);
+}
+
+// rcosdesign(0.5, 10, 2, 'sqrt') (Tester.m:112; OFDM.c:32 holds the same values as floats), as ofdm_captures.hip
+static void stream_taps(float out[21]) {
+    const double beta = 0.5, sps = 2.0, pi = M_PI;
+    double h[21], e = 0.0;
+    for (int i = 0; i < 21; ++i) {
+        const double t = (i - 10) / sps, q = 4 * beta * t;
+        double b;
+        if (t == 0.0) b = -1.0 / (pi * sps) * (pi * (beta - 1) - 4 * beta);
+        else if (std::fabs(std::fabs(q) - 1.0) < 1e-12)
+            b = 1.0 / (2 * pi * sps) * (pi * (beta + 1) * std::sin(pi * (beta + 1) / (4 * beta)) -
+                                        4 * beta * std::sin(pi * (beta - 1) / (4 * beta)) +
+                                        pi * (beta - 1) * std::cos(pi * (beta - 1) / (4 * beta)));
+        else
+            b = -4 * beta / sps * (std::cos((1 + beta) * pi * t) + std::sin((1 - beta) * pi * t) / q) / (pi * (q * q - 1));
+        h[i] = b;
+        e += b * b;
+    }
+    for (int i = 0; i < 21; ++i) out[i] = (float)(h[i] / std::sqrt(e));
+    for (int i = 0; i < 10; ++i) out[20 - i] = out[i];
+}
+
+}  // namespace ofdm
+
+using namespace ofdm;
+
+extern "C" int ofdm_receive_stream(ofdm_ctx *ctx, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
+                                   int payload, int64_t max_packets, void *d_packets, void *d_count, void *d_bits,
+                                   void *d_eq, void *d_counters, void *d_metric, void *d_cross) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c) return set_error(OFDM_E_ARG, "ctx is NULL");
+    if (!opts) return set_error(OFDM_E_ARG, "opts is NULL");
+    if (n_samples < 0) return set_error(OFDM_E_ARG, "n_samples %lld is negative", (long long)n_samples);
+    if (max_packets < 0) return set_error(OFDM_E_ARG, "max_packets %lld is negative", (long long)max_packets);
+    if (payload != OFDM_PAYLOAD_MESSAGE && payload != OFDM_PAYLOAD_TESTER)
+        return set_error(OFDM_E_ARG, "a stream is decoded against a fixed payload (MESSAGE or TESTER), got %d", payload);
+    if (opts->word_stats) return set_error(OFDM_E_ARG, "word_stats is not available for a stream");
+    if (!d_count) return set_error(OFDM_E_ARG, "d_count is required");
+    if (!d_samples && n_samples > 0) return set_error(OFDM_E_ARG, "d_samples is required");
+    if (!d_packets && max_packets > 0) return set_error(OFDM_E_ARG, "d_packets is required");
+    if (reinterpret_cast<uintptr_t>(d_samples) & 7u) return set_error(OFDM_E_ARG, "d_samples must be 8-byte aligned");
+    if (hipSetDevice(c->device) != hipSuccess) return set_error(OFDM_E_HIP, "hipSetDevice(%d) failed", c->device);
+    if (n_samples < 48) {                                            // no positions, no packets
+        if (hipMemsetAsync(d_count, 0, 2 * sizeof(int64_t), c->stream) != hipSuccess)
+            return set_error(OFDM_E_HIP, "hipMemsetAsync(d_count) failed");
+        return OFDM_OK;
+    }
+    DecArgs da{};
+    uint32_t table[3 * LONG_MAX_FRAMES];
+    da.n_data = payload_table_long(payload, c->message, table);
+    for (int d = 0; d < da.n_data; ++d) demap_words(table + 3 * d, da.dtable + 4 * d);
+    const int nfr = 320 + 80 * da.n_data;
+    // the decode block's LDS, checked before anything is launched
+    da.plane = (2 * nfr + 19 + 3) & ~3;
+    const int spec_floats = (4 * ((da.n_data + 2) / 3) + 1) * SDEC_SPEC_PITCH;
+    da.wave_floats = (std::max(2 * da.plane + 2 * nfr, spec_floats) + 3) & ~3;
+    int lds_max = 0;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) != hipSuccess || lds_max <= 0)
+        return set_error(OFDM_E_HIP, "cannot query the device's LDS size");
+    const size_t limit = std::min<size_t>((size_t)lds_max, SDEC_LDS_PER_CU);
+    const size_t head = SDEC_ACC_WORDS * sizeof(unsigned long long), per_wave = (size_t)da.wave_floats * sizeof(float);
+    if (head + per_wave > limit)
+        return set_error(OFDM_E_ARG, "a %d-symbol packet needs %zu bytes of LDS, above the %zu available", da.n_data,
+                         head + per_wave, limit);
+    const int W = (int)std::min<int64_t>(std::min<int64_t>(SDEC_MAX_WAVES, (int64_t)((limit - head) / per_wave)),
+                                         std::max<int64_t>(max_packets, 1));
+    const size_t lds = head + (size_t)W * per_wave;
+    if (lds > limit) return set_error(OFDM_E_ARG, "dynamic LDS request %zu above the limit %zu", lds, limit);
+
+    // scratch: the crossing bitmap (whole 16-byte groups), the front slots, the selection blocks' counts and maxima
+    const int64_t lc = n_samples - 47;
+    const int64_t words = (lc + 31) / 32, tiles = (lc + SD_TILE - 1) / SD_TILE;
+    const int64_t nslots = (lc + SS_SLOT - 1) / SS_SLOT, nblocks = (nslots + SS_THREADS - 1) / SS_THREADS;
+    if (tiles > 0x7fffffffll || nblocks > 0x7fffffffll)
+        return set_error(OFDM_E_ARG, "n_samples %lld is beyond one launch", (long long)n_samples);
+    const size_t bm_bytes = (size_t)((words + 3) & ~(int64_t)3) * 4;
+    const size_t total = bm_bytes + (size_t)(nslots + 2 * nblocks) * sizeof(int64_t);
+    int rc = c->ensure(&c->d_scratch2, &c->cap_scratch2, total);
+    if (rc) return rc;
+    char *base = (char *)c->d_scratch2;
+
+    DetArgs ta{};
+    ta.x = (const float2 *)d_samples;
+    ta.n = n_samples;
+    ta.lc = lc;
+    ta.tiles = tiles;
+    ta.words = words;
+    ta.bitmap = (uint32_t *)base;
+    ta.cross = (uint32_t *)d_cross;
+    ta.metric = (float *)d_metric;
+    SelArgs sa{};
+    sa.bitmap = ta.bitmap;
+    sa.lc = lc;
+    sa.nslots = nslots;
+    sa.nblocks = nblocks;
+    sa.max_packets = max_packets;
+    sa.slots = (int64_t *)(base + bm_bytes);
+    sa.blk_cnt = sa.slots + nslots;
+    sa.blk_max = sa.blk_cnt + nblocks;
+    sa.count = (int64_t *)d_count;
+    sa.pk = (ofdm_stream_packet *)d_packets;
+
+    // one tile per block up to a grid the loop in the kernel wraps (the results do not depend on it)
+    const dim3 dgrid((unsigned)std::min<int64_t>(tiles, 1 << 20));
+    c->tic(OFDM_K_STREAM_DETECT);
+    if (ta.metric) hipLaunchKernelGGL(stream_detect_kernel<true>, dgrid, dim3(SD_THREADS), 0, c->stream, ta);
+    else hipLaunchKernelGGL(stream_detect_kernel<false>, dgrid, dim3(SD_THREADS), 0, c->stream, ta);
+    c->toc();
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(OFDM_E_HIP, "stream_detect_kernel launch: %s", hipGetErrorString(e));
+    c->tic(OFDM_K_STREAM_SELECT);
+    hipLaunchKernelGGL(stream_select_kernel<0>, dim3((unsigned)nblocks), dim3(SS_THREADS), 0, c->stream, sa);
+    hipLaunchKernelGGL(stream_select_kernel<1>, dim3(1), dim3(SS_SCAN_THREADS), 0, c->stream, sa);
+    hipLaunchKernelGGL(stream_select_kernel<2>, dim3((unsigned)nblocks), dim3(SS_THREADS), 0, c->stream, sa);
+    c->toc();
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_error(OFDM_E_HIP, "stream_select_kernel launch: %s", hipGetErrorString(e));
+    if (max_packets == 0) return OFDM_OK;
+
+    da.x = ta.x;
+    da.n = n_samples;
+    da.count = sa.count;
+    da.pk = sa.pk;
+    da.bits = (uint32_t *)d_bits;
+    da.eq = (float2 *)d_eq;
+    da.counters = (unsigned long long *)d_counters;
+    da.float_cfo = opts->float_cfo;
+    stream_taps(da.taps);
+    // the packet count stays on the device: enough blocks for max_packets, at most two per CU; the waves loop over d_count
+    const int64_t blocks = (max_packets + W - 1) / W;
+    const dim3 grid((unsigned)std::min<int64_t>(blocks, 2 * (int64_t)c->cus));
+    c->tic(OFDM_K_STREAM_DECODE);
+    if (da.bits || da.eq) hipLaunchKernelGGL(stream_decode_kernel<true>, grid, dim3(64 * W), lds, c->stream, da);
+    else hipLaunchKernelGGL(stream_decode_kernel<false>, grid, dim3(64 * W), lds, c->stream, da);
+    c->toc();
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_error(OFDM_E_HIP, "stream_decode_kernel launch: %s", hipGetErrorString(e));
+    return OFDM_OK;
+}

@@ -3,7 +3,8 @@
 Mirrors the reference's three hot-path functions (src/OFDM.c):
     Transmitter()            OFDM.c:467-618   -> Engine.transmitter() / Engine.tx_frames()
     Transmission_Over_Air()  OFDM.c:635-655   -> Engine.transmission_over_air()
-    Receiver()               OFDM.c:941-1165  -> Engine.receiver() / Engine.rx_frames() / Engine.receive_captures()
+    Receiver()               OFDM.c:941-1165  -> Engine.receiver() / Engine.rx_frames() / Engine.receive_captures() /
+                                                 Engine.receive_stream() (every packet of one recording)
 and main()'s SNR loop (OFDM.c:1187-1222) -> Engine.symbol_sweep() / Engine.frame_sweep().
 All arithmetic happens in the HIP kernels of libofdm_mi355x.so.
 """
@@ -302,6 +303,84 @@ class Engine:
             host = bits if from_numpy else bits.cpu().numpy()
             messages = [decode_message(row) for row in host]
         return dict(records=records, bits=bits, eq=eq, messages=messages, frames=nd, cap_len=L)
+
+    def receive_stream(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
+                       want_bits: bool = True, want_eq: bool = False, want_metric: bool = False,
+                       want_cross: bool = False, counters=None) -> dict:
+        """Every packet of one recording of any length (ofdm_receive_stream, include/ofdm_mi355x_stream.h): the
+        reference's detection rule once over the whole recording, then the receiver chain on every packet found.
+
+        samples: a one-dimensional contiguous torch complex64 tensor on this engine's device, used in place (never
+        written), or a numpy complex64 array, uploaded once.  Anything else raises ValueError before any launch.
+        max_packets: records to decode at most, default n // 301 + 1 (no stream holds more fronts).  counters: an int64
+        device tensor of NCOUNTERS elements, added to.
+        Returns count (records written), found (packets in the stream), positions (int64 [count]), records (a
+        structured host array, abi.stream_packet_dtype()), bits ([count, 96 D] int32), eq ([count, 48 D] complex64),
+        messages, metric (float32 [n - 47]) and cross (uint32 words, stream.unpack_cross) -- those not asked for None;
+        bits, eq, metric and cross stay on the device for torch input.  The call reads the packet count back, so it
+        waits for the device."""
+        torch = _torch()
+        opts = make_rx_opts(mode)
+        nd = self.payload_frames(payload)
+        dev = torch.device("cuda", self.device)
+        from_numpy = isinstance(samples, np.ndarray)
+        if from_numpy:
+            if samples.dtype != np.complex64 or samples.ndim != 1:
+                raise ValueError(f"samples must be complex64 [n], got {samples.dtype} {samples.shape}")
+            t = torch.from_numpy(np.ascontiguousarray(samples)).to(dev)
+        elif torch.is_tensor(samples):
+            t = samples
+        else:
+            raise ValueError(f"samples must be a torch tensor or a numpy array, got {type(samples).__name__}")
+        if t.dtype != torch.complex64 or t.dim() != 1:
+            raise ValueError(f"samples must be complex64 [n], got {t.dtype} {tuple(t.shape)}")
+        if t.device != dev:
+            raise ValueError(f"samples are on {t.device}, the engine runs on {dev}")
+        n = int(t.shape[0])
+        if n > 1 and t.stride(0) != 1:
+            raise ValueError(f"samples need a unit stride, got {t.stride(0)}")
+        if max_packets is None:
+            max_packets = n // 301 + 1
+        if int(max_packets) != max_packets or max_packets < 0:
+            raise ValueError(f"max_packets must be a non-negative integer, got {max_packets!r}")
+        max_packets = int(max_packets)
+        if counters is not None:
+            if not (torch.is_tensor(counters) and counters.dtype == torch.int64 and counters.device == dev
+                    and counters.numel() == abi.NCOUNTERS and counters.is_contiguous()):
+                raise ValueError("counters must be a contiguous int64 device tensor of NCOUNTERS elements")
+        lc = max(n - 47, 0)
+        rows = max(max_packets, 1)                                    # a pointer even when nothing may be written
+        pk = torch.empty((rows, C.sizeof(abi.StreamPacket)), dtype=torch.uint8, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        words = torch.empty((rows, 3 * nd), dtype=torch.int32, device=dev) if want_bits else None
+        eq = torch.empty((rows, 48 * nd), dtype=torch.complex64, device=dev) if want_eq else None
+        metric = torch.empty(max(lc, 1), dtype=torch.float32, device=dev) if want_metric else None
+        cross = torch.empty(max((lc + 31) // 32, 1), dtype=torch.int32, device=dev) if want_cross else None
+        opt = lambda x: None if x is None else _ptr(x)
+        check(self.lib, self.lib.ofdm_receive_stream(
+            self.ctx, _ptr(t) if n else None, n, C.byref(opts), abi.PAYLOAD[payload], max_packets, _ptr(pk), _ptr(cnt),
+            opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream")
+        found, count = (int(v) for v in cnt.cpu())
+        records = pk[:count].cpu().numpy().view(abi.stream_packet_dtype()).reshape(count)
+        bits = None
+        if want_bits:
+            sh = torch.arange(31, -1, -1, dtype=torch.int32, device=dev)
+            bits = ((words[:count].unsqueeze(-1) >> sh) & 1).reshape(count, 96 * nd)          # MSB first
+        eq = None if eq is None else eq[:count]
+        metric = None if metric is None else metric[:lc]
+        cross = None if cross is None else cross[:(lc + 31) // 32]
+        messages = None
+        if want_bits:
+            host = bits.cpu().numpy()
+            messages = [decode_message(row) for row in host]
+            if from_numpy:
+                bits = host
+        if from_numpy:
+            eq = None if eq is None else eq.cpu().numpy()
+            metric = None if metric is None else metric.cpu().numpy()
+            cross = None if cross is None else cross.cpu().numpy().view(np.uint32)
+        return dict(count=count, found=found, positions=records["packet_pos"].copy(), records=records, bits=bits,
+                    eq=eq, messages=messages, metric=metric, cross=cross, frames=nd)
 
     def word_length_report(self, capture: np.ndarray) -> dict:
         """Word_Optimization_Analysis (OFDM.c:38-73) of the capture's RRC matched-filter output."""

@@ -1,0 +1,135 @@
+"""The stream receiver's rule in numpy, and its command line.
+
+select_packets() is the executable specification of include/ofdm_mi355x_stream.h: the reference's Packet_Selection
+(OFDM.c:685-771) over a whole recording, reporting every confirmed front instead of the first one.  The kernels
+(csrc/ofdm_stream.hip) are tested against it bit for bit; it is host code for tests and tools and is never on a hot
+path.  main() is `python ofdm_pkg.py stream`.
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import sys
+from pathlib import Path
+
+import numpy as np
+
+THRESHOLD = 0.75          # OFDM.c:701
+FRONT_GAP = 300           # a front's previous crossing is more than this far back (OFDM.c:716-741)
+CONFIRM = 230             # the second look, front + 230 (OFDM.c:745-760)
+PACKET_OFFSET = 11        # len_RRC_rx + 1 (OFDM.c:758)
+LAST_FRONT = 4            # OFDM_STREAM_LAST_FRONT
+
+
+def unpack_cross(words, lc: int) -> np.ndarray:
+    """The crossing bitmap of ofdm_receive_stream (bit i & 31 of word i >> 5) as a boolean array of lc positions."""
+    w = np.ascontiguousarray(np.asarray(words).astype(np.uint32, copy=False))
+    if len(w) < (lc + 31) // 32:
+        raise ValueError(f"{len(w)} words do not hold {lc} positions")
+    bits = np.unpackbits(w.view(np.uint8), bitorder="little")
+    return bits[:lc].astype(bool)
+
+
+def select_packets(cross_or_metric, thr: float = THRESHOLD) -> dict:
+    """Every packet of a stream from its crossings (a boolean array) or its metric M (a float array, crossing where
+    M > thr; NaN is no crossing).
+
+    crossing  M[i] > thr
+    front     a crossing i whose previous crossing b (-1 when there is none) has i - b > 300
+    confirmed a front with i + 230 < Lc and a crossing at i + 230
+    packets   every confirmed front, ascending, at front + 11; flag LAST_FRONT (4) on the packet whose front is the
+              largest front of the stream, confirmed or not
+
+    Returns fronts, confirmed (a mask over fronts), positions (int64) and flags (int32, 0 or 4)."""
+    a = np.asarray(cross_or_metric)
+    if a.ndim != 1:
+        raise ValueError("one-dimensional crossings or metric expected")
+    if a.dtype == bool:
+        cross = a
+    else:
+        with np.errstate(invalid="ignore"):
+            cross = a > thr
+    lc = len(cross)
+    idx = np.nonzero(cross)[0].astype(np.int64)
+    prev = np.concatenate([[-1], idx[:-1]]).astype(np.int64)
+    fronts = idx[(idx - prev) > FRONT_GAP]
+    look = fronts + CONFIRM
+    conf = np.zeros(len(fronts), bool)
+    inside = look < lc
+    conf[inside] = cross[look[inside]]
+    pos = fronts[conf] + PACKET_OFFSET
+    flags = np.zeros(len(pos), np.int32)
+    if len(fronts):
+        flags[fronts[conf] == fronts.max()] = LAST_FRONT
+    return dict(fronts=fronts, confirmed=conf, positions=pos.astype(np.int64), flags=flags)
+
+
+def first_packet(sel: dict) -> int:
+    """Packet_Selection's answer from select_packets': the first packet that is not the last front's, 0 when none."""
+    keep = sel["positions"][sel["flags"] & LAST_FRONT == 0]
+    return int(keep[0]) if len(keep) else 0
+
+
+def synthetic_segments(period: int, frames: int, gap: int) -> list:
+    """`frames` whole frames of the repeated waveform, each behind an idle gap, and a closing gap"""
+    seg = []
+    for k in range(frames):
+        seg += [("gap", gap), ("wave", (k % 10) * period, (k % 10 + 1) * period)]
+    return seg + [("gap", gap)]
+
+
+def main(argv=None) -> int:
+    """python ofdm_pkg.py stream: decode every packet of a recording (--in rec.npy, complex64) or of a synthetic
+    stream; one line per packet and packets.csv under --out."""
+    ap = argparse.ArgumentParser(prog="ofdm_pkg.py stream", description=main.__doc__)
+    ap.add_argument("--in", dest="rec", help="a .npy file of complex samples at 40 MS/s")
+    ap.add_argument("--out", default="stream_out")
+    ap.add_argument("--message", default=None, help="the MESSAGE payload packets are checked against")
+    ap.add_argument("--frames", type=int, default=8, help="synthetic stream: packets")
+    ap.add_argument("--gap", type=int, default=500, help="synthetic stream: idle samples between packets")
+    ap.add_argument("--snr", type=float, default=20.0)
+    ap.add_argument("--cfo-hz", type=float, default=0.0)
+    ap.add_argument("--taps", default=None, help="multipath FIR, e.g. 1,0,0.4+0.3j")
+    ap.add_argument("--noise", default="real", choices=("real", "complex", "none"))
+    ap.add_argument("--seed", type=int, default=0x80211A)
+    ap.add_argument("--max-packets", type=int, default=None)
+    a = ap.parse_args(argv)
+    import torch  # noqa: PLC0415
+    from . import abi  # noqa: PLC0415
+    from .channel import make_stream, parse_taps  # noqa: PLC0415
+    from .engine import Engine  # noqa: PLC0415
+    with Engine(0) as eng:
+        if a.message is not None:
+            eng.set_long_message(a.message)
+        if a.rec:
+            x = np.load(a.rec)
+            if x.ndim != 1 or not np.iscomplexobj(x):
+                raise SystemExit(f"{a.rec}: a one-dimensional complex array expected, got {x.dtype} {x.shape}")
+            samples = torch.from_numpy(np.ascontiguousarray(x, np.complex64)).cuda()
+        else:
+            w = torch.from_numpy(eng.transmitter("c", "message")).cuda()
+            gen = torch.Generator(device="cuda")
+            gen.manual_seed(a.seed)
+            samples = make_stream(w, synthetic_segments(len(w) // 10, a.frames, a.gap), a.snr, a.cfo_hz,
+                                  taps=None if a.taps is None else parse_taps(a.taps), noise=a.noise, generator=gen)
+        out = eng.receive_stream(samples, max_packets=a.max_packets)
+    rec = out["records"]
+    d = Path(a.out)
+    d.mkdir(parents=True, exist_ok=True)
+    with open(d / "packets.csv", "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["packet_pos", "flags", "cfo_coarse_hz", "cfo_fine_hz", "bit_err", "evm_db_pre", "message"])
+        for k in range(out["count"]):
+            r = rec[k]
+            row = [int(r["packet_pos"]), int(r["flags"]), float(r["cfo_coarse_hz"]), float(r["cfo_fine_hz"]),
+                   int(r["bit_err"]), float(r["evm_db_pre"]), out["messages"][k]]
+            wr.writerow(row)
+            tags = "".join(t for bit, t in ((abi.CAPTURE_OOB, " oob"), (abi.STREAM_LAST_FRONT, " last-front")) if row[1] & bit)
+            print(f"{row[0]:>12d}  flags {row[1]}{tags:<15s} cfo {row[2] + row[3]:+10.1f} Hz  bit_err {row[4]:4d}  {row[6]!r}")
+    print(f"{out['found']} packets found, {out['count']} decoded of {len(samples)} samples -> {d / 'packets.csv'}",
+          file=sys.stderr)
+    return 0
+
+
+__all__ = ["select_packets", "unpack_cross", "first_packet", "synthetic_segments", "main",
+           "THRESHOLD", "FRONT_GAP", "CONFIRM", "PACKET_OFFSET", "LAST_FRONT"]

@@ -33,6 +33,7 @@ if __name__ == "__main__":
     # python ofdm_pkg.py build [--force]      compile libofdm_mi355x.so
     # python ofdm_pkg.py sweep [args...]      OFDM.c main() on the GPU (see ofdm_amd.sweep)
     # python ofdm_pkg.py captures [args...]   BER / EVM under CFO, multipath, complex noise (ofdm_amd.sweep.captures_main)
+    # python ofdm_pkg.py stream [args...]     every packet of a recording or a synthetic stream (ofdm_amd.stream.main)
     cmd = sys.argv[1] if len(sys.argv) > 1 else "build"
     if cmd == "sweep":
         load()
@@ -42,5 +43,9 @@ if __name__ == "__main__":
         load()
         from ofdm_amd import sweep  # noqa: PLC0415
         sweep.captures_main(sys.argv[2:])
+    elif cmd == "stream":
+        load()
+        from ofdm_amd import stream  # noqa: PLC0415
+        raise SystemExit(stream.main(sys.argv[2:]))
     else:
         print(build(force="--force" in sys.argv))
