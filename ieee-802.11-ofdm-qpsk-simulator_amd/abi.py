@@ -32,6 +32,7 @@ EVM_Q_SCALE = float(1 << 20)
 # kernel ids for timing
 K_FFT, K_TX, K_RX, K_FRAME = range(4)
 K_STREAM_DETECT, K_STREAM_SELECT, K_STREAM_DECODE = 4, 5, 6     # OFDM_K_STREAM_* (ofdm_mi355x_stream.h)
+K_TRANSMIT = 7                                                   # OFDM_K_TRANSMIT (ofdm_mi355x_tx.h)
 
 # every entry point of the header, with ctypes argument types
 _V = C.c_void_p
@@ -97,6 +98,16 @@ STREAM_EXPORTS = tuple(_STREAM_SIGS)
 STREAM_LAST_FRONT = 4              # OFDM_STREAM_LAST_FRONT, ofdm_capture_result.flags bit 2
 STREAM_RUN, STREAM_TILE = 31, 7936  # OFDM_STREAM_RUN, OFDM_STREAM_TILE
 
+# the extension header include/ofdm_mi355x_tx.h (Transmitter() over a device-resident batch of per-packet payloads,
+# written into a device-resident recording); the export lists above and ABI_VERSION do not change with it
+TX_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_tx.h"
+_TX_SIGS = {
+    "ofdm_transmit_len": (C.c_int, [C.c_int32, C.POINTER(C.c_int32)]),
+    "ofdm_transmit_packets": (C.c_int, [_V, _V, _V, C.c_int64, _V, C.c_int64, C.c_int64, _V, _V, _V, C.c_int64]),
+}
+TX_EXPORTS = list(_TX_SIGS)
+TX_ACCUMULATE = 1                  # OFDM_TX_ACCUMULATE, ofdm_tx_opts.flags bit 0
+
 
 class OfdmError(RuntimeError):
     pass
@@ -114,6 +125,11 @@ class RxOpts(C.Structure):
     _fields_ = [("cap_len", C.c_int32), ("float_cfo", C.c_int32), ("matlab_slicer", C.c_int32),
                 ("float_taps", C.c_int32), ("fixed_start", C.c_int32), ("word_stats", C.c_int32),
                 ("reserved", C.c_int32 * 2)]
+
+
+class TxOpts(C.Structure):
+    """ofdm_tx_opts (16 bytes)"""
+    _fields_ = [("conv", C.c_int32), ("float_taps", C.c_int32), ("n_data", C.c_int32), ("flags", C.c_int32)]
 
 
 class CaptureResult(C.Structure):
@@ -174,6 +190,11 @@ def wave_len(frames: int) -> int:
     return 10 * (2 * (320 + 80 * frames) + 20)
 
 
+def packet_len(frames: int) -> int:
+    """One period of Transmitter() for `frames` data symbols, a packet of ofdm_transmit_packets: 2 (320 + 80 D) + 20."""
+    return 2 * (320 + 80 * frames) + 20
+
+
 def capture_len(frames: int) -> int:
     """Receiver() capture, int(0.307 x waveform length) (OFDM.c:945): 3008 for D = 2."""
     return int(wave_len(frames) * 0.307)
@@ -216,7 +237,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
         raise OfdmError(f"{p} not found: the HIP library must be built (build_lib.build()); "
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS}.items():
+    for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

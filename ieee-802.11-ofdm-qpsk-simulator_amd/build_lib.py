@@ -20,7 +20,7 @@ BUILD = PKG_DIR / "_build"
 LIB = PKG_DIR / "libofdm_mi355x.so"
 SOURCES = ["ofdm_capi.hip", "ofdm_symbol.hip", "ofdm_rxpack.hip", "ofdm_rxpack_ideal.hip", "ofdm_frame.hip",
            "ofdm_frame_sym.hip", "ofdm_frame_fix.hip", "ofdm_frame_long.hip", "ofdm_frame_xl.hip",
-           "ofdm_captures.hip", "ofdm_stream.hip"]
+           "ofdm_captures.hip", "ofdm_stream.hip", "ofdm_transmit.hip"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: keep f32 math scalar (packed v_pk_* f32 gives no rate on gfx950 and its
@@ -38,7 +38,8 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vecto
 # interleaved: frame +0.9 % over max-ILP; frame8 +0.8 % over the default -- iterative-ILP +0.7 %, but the compiler
 # fails on that TU with -g, which tools/frame8_mix.py needs; the symbol kernel's TU is best at the default,
 # profiles/r06/frame/ab_sched.txt).  The long-message kernels (ofdm_frame_xl.hip) and the batched receiver for
-# caller-supplied captures (ofdm_captures.hip) keep the default scheduler, as does the stream receiver (ofdm_stream.hip).
+# caller-supplied captures (ofdm_captures.hip) keep the default scheduler, as do the stream receiver (ofdm_stream.hip)
+# and the packet transmitter (ofdm_transmit.hip).
 SOURCE_FLAGS = {"ofdm_symbol.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 "ofdm_rxpack.hip": os.environ.get("OFDM_RXPACK_FLAGS", "-mllvm -amdgpu-sched-strategy=max-ilp").split(),
                 "ofdm_rxpack_ideal.hip": os.environ.get("OFDM_RXPACK_IDEAL_FLAGS", "").split(),
@@ -50,7 +51,8 @@ SOURCE_FLAGS = {"ofdm_symbol.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                                                       "-mllvm -amdgpu-sched-strategy=max-ilp").split(),
                 "ofdm_frame_xl.hip": os.environ.get("OFDM_FRAME_XL_FLAGS", "").split(),
                 "ofdm_captures.hip": os.environ.get("OFDM_CAPTURES_FLAGS", "").split(),
-                "ofdm_stream.hip": os.environ.get("OFDM_STREAM_FLAGS", "").split()}
+                "ofdm_stream.hip": os.environ.get("OFDM_STREAM_FLAGS", "").split(),
+                "ofdm_transmit.hip": os.environ.get("OFDM_TRANSMIT_FLAGS", "").split()}
 
 
 # Kernels whose parity-dump variants (last template argument `true`) are allowed to spill: they

@@ -103,8 +103,22 @@ def make_stream(wave, segments, snr_db, cfo_hz=0.0, taps=None, noise: str = "rea
         else:
             raise ValueError(f"a segment is ('gap', n >= 0) or ('wave', lo, hi) with 0 <= lo <= hi, got {seg!r}")
     x = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.complex64, device=dev)
-    n = int(x.shape[0])
     power = float(torch.mean(wave.real.double() ** 2 + wave.imag.double() ** 2))        # OFDM.c:637-643
+    return impair_stream(x, power, snr_db, cfo_hz, taps=taps, noise=noise, generator=generator)
+
+
+def impair_stream(x, power: float, snr_db, cfo_hz=0.0, taps=None, noise: str = "real", generator=None):
+    """make_stream's impairments over a recording `x` (complex64 [n]) that is already laid out -- by make_stream, or by
+    Engine.transmit_packets: the multipath FIR truncated to the recording's length, the rotation
+    exp(j 2 pi cfo_hz k 25e-9) by the stream index k, then noise of variance power / 10^(snr_db / 10) over gaps and
+    packets alike ("real": all of it in the real part, "complex": split across both axes, "none": nothing).  x is not
+    written; the result is on x's device (x itself when nothing applies)."""
+    torch = _torch()
+    if noise not in NOISE_KINDS:
+        raise ValueError(f"noise must be one of {NOISE_KINDS}, got {noise!r}")
+    if not torch.is_tensor(x) or x.dim() != 1 or x.dtype != torch.complex64:
+        raise ValueError("x must be a one-dimensional complex64 tensor")
+    dev, n = x.device, int(x.shape[0])
     y = x
     if taps is not None:
         h = np.asarray(taps, np.complex64).ravel()
@@ -134,4 +148,4 @@ def parse_taps(text: str) -> np.ndarray:
     return np.array([complex(t.strip()) for t in text.split(",") if t.strip()], np.complex64)
 
 
-__all__ = ["make_captures", "make_stream", "parse_taps", "TS_OVERSAMPLED"]
+__all__ = ["make_captures", "make_stream", "impair_stream", "parse_taps", "TS_OVERSAMPLED"]

@@ -208,6 +208,100 @@ class Engine:
                                                   buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "transmitter")
         return buf[:2 * n.value].view(np.complex64).copy()
 
+    def transmit_packets(self, words, n_data: int, positions=None, pos0: int = 0, stride: int | None = None,
+                         gains=None, cfo_hz=None, out=None, n_out: int | None = None, accumulate: bool = False,
+                         conv: str = "c", float_taps: bool = True):
+        """Transmitter() over a batch of per-packet payloads, written into one device-resident recording
+        (ofdm_transmit_packets, include/ofdm_mi355x_tx.h); returns the recording, a torch complex64 device tensor.
+
+        words: uint32 / int32 [n, 3 n_data] payload words (stream.pack_messages; the `words` layout behind
+        receive_stream's bits), a torch tensor on this engine's device used in place, or a numpy array, uploaded.
+        Packet k starts at positions[k] (int64 [n], torch on the device or numpy) or at pos0 + k stride, stride
+        defaulting to the packet length P = abi.packet_len(n_data); samples outside the recording are dropped.
+        gains (complex64 [n]) and cfo_hz (float32 [n]) are optional, torch on the device or numpy.  out: the recording
+        to write into, a contiguous complex64 device tensor, used in place; otherwise a zero-filled one of n_out
+        samples is allocated, by default just large enough for the dense layout pos0 + n stride (pos0 >= 0), or for the
+        furthest packet when positions is a numpy array.  accumulate adds to the recording (fp32 atomic adds) instead
+        of storing.  Anything malformed raises ValueError before any launch.  The call waits for the device only when it
+        uploaded numpy inputs (their device copies are released on return)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        if int(n_data) != n_data or not 1 <= n_data <= abi.LONG_MAX_DATA_SYMBOLS:
+            raise ValueError(f"n_data must be an integer in [1, {abi.LONG_MAX_DATA_SYMBOLS}], got {n_data!r}")
+        n_data = int(n_data)
+        if conv not in abi.CONV:
+            raise ValueError(f"conv must be one of {tuple(abi.CONV)}, got {conv!r}")
+        plen = abi.packet_len(n_data)
+
+        uploaded = []
+
+        def device_array(x, name, np_dtypes, torch_dtypes, shape_text, ndim):
+            if isinstance(x, np.ndarray):
+                if x.dtype not in np_dtypes or x.ndim != ndim:
+                    raise ValueError(f"{name} must be {shape_text}, got {x.dtype} {x.shape}")
+                uploaded.append(name)
+                return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+            if not torch.is_tensor(x):
+                raise ValueError(f"{name} must be a torch tensor or a numpy array, got {type(x).__name__}")
+            if x.dtype not in torch_dtypes or x.dim() != ndim:
+                raise ValueError(f"{name} must be {shape_text}, got {x.dtype} {tuple(x.shape)}")
+            if x.device != dev:
+                raise ValueError(f"{name} is on {x.device}, the engine runs on {dev}")
+            if not x.is_contiguous():
+                raise ValueError(f"{name} must be contiguous, got strides {x.stride()}")
+            return x
+
+        if isinstance(words, np.ndarray) and words.dtype == np.uint32:
+            words = words.view(np.int32)                                  # torch has no uint32 arithmetic; same bits
+        w = device_array(words, "words", (np.dtype(np.int32),), (torch.int32, getattr(torch, "uint32", torch.int32)),
+                         f"uint32 / int32 [n, {3 * n_data}]", 2)
+        if w.shape[1] != 3 * n_data:
+            raise ValueError(f"words must be uint32 / int32 [n, {3 * n_data}], got {tuple(w.shape)}")
+        n = int(w.shape[0])
+        per_packet = (("positions", positions, (np.dtype(np.int64),), (torch.int64,), "int64 [n]"),
+                      ("gains", gains, (np.dtype(np.complex64),), (torch.complex64,), "complex64 [n]"),
+                      ("cfo_hz", cfo_hz, (np.dtype(np.float32),), (torch.float32,), "float32 [n]"))
+        dv = {}
+        for name, x, npd, td, text in per_packet:
+            dv[name] = None if x is None else device_array(x, name, npd, td, text, 1)
+            if dv[name] is not None and int(dv[name].shape[0]) != n:
+                raise ValueError(f"{name} must be {text} with n = {n}, got {tuple(dv[name].shape)}")
+        if stride is None:
+            stride = plen
+        if int(pos0) != pos0 or int(stride) != stride:
+            raise ValueError(f"pos0 and stride must be integers, got {pos0!r}, {stride!r}")
+        pos0, stride = int(pos0), int(stride)
+        if out is not None:
+            if not (torch.is_tensor(out) and out.dtype == torch.complex64 and out.dim() == 1):
+                raise ValueError("out must be a one-dimensional torch complex64 tensor")
+            if out.device != dev:
+                raise ValueError(f"out is on {out.device}, the engine runs on {dev}")
+            if out.shape[0] > 1 and out.stride(0) != 1:
+                raise ValueError(f"out needs a unit stride, got {out.stride(0)}")
+            if n_out is not None and int(n_out) != int(out.shape[0]):
+                raise ValueError(f"n_out {n_out!r} does not match out's {int(out.shape[0])} samples")
+            rec = out
+        else:
+            if n_out is None:
+                if positions is None:
+                    n_out = max(pos0 + (n - 1) * stride, pos0) + plen if n else 0
+                elif isinstance(positions, np.ndarray):
+                    n_out = int(positions.max()) + plen if n else 0
+                else:
+                    raise ValueError("n_out or out is required when positions is a device tensor")
+            if int(n_out) != n_out or n_out < 0:
+                raise ValueError(f"n_out must be a non-negative integer, got {n_out!r}")
+            rec = torch.zeros(int(n_out), dtype=torch.complex64, device=dev)
+        opts = abi.TxOpts(abi.CONV[conv], int(bool(float_taps)), n_data, abi.TX_ACCUMULATE if accumulate else 0)
+        opt = lambda x: None if x is None else _ptr(x)
+        n_rec = int(rec.shape[0])
+        check(self.lib, self.lib.ofdm_transmit_packets(
+            self.ctx, C.byref(opts), _ptr(w) if n else None, n, opt(dv["positions"]), pos0, stride, opt(dv["gains"]),
+            opt(dv["cfo_hz"]), _ptr(rec) if n_rec else None, n_rec), "transmit_packets")
+        if uploaded:
+            self.synchronize()
+        return rec
+
     def transmission_over_air(self, tx: np.ndarray, snr_db: float, seed: int = 0x80211A, trial: int = 0,
                               snr_index: int = 0) -> np.ndarray:
         tx = np.ascontiguousarray(tx, np.complex64)

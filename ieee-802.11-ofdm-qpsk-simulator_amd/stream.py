@@ -1,9 +1,10 @@
-"""The stream receiver's rule in numpy, and its command line.
+"""The stream receiver's rule in numpy, and the command lines of the stream receiver and the packet transmitter.
 
 select_packets() is the executable specification of include/ofdm_mi355x_stream.h: the reference's Packet_Selection
 (OFDM.c:685-771) over a whole recording, reporting every confirmed front instead of the first one.  The kernels
 (csrc/ofdm_stream.hip) are tested against it bit for bit; it is host code for tests and tools and is never on a hot
-path.  main() is `python ofdm_pkg.py stream`.
+path.  main() is `python ofdm_pkg.py stream`.  pack_messages() packs texts into the payload words both the receivers'
+d_bits and ofdm_transmit_packets' d_words use; transmit_main() is `python ofdm_pkg.py transmit`.
 """
 from __future__ import annotations
 
@@ -78,6 +79,76 @@ def synthetic_segments(period: int, frames: int, gap: int) -> list:
     return seg + [("gap", gap)]
 
 
+MAX_DATA_SYMBOLS = 15     # OFDM_LONG_MAX_DATA_SYMBOLS
+
+
+def pack_messages(texts, n_data: int | None = None):
+    """Payload words of one packet per text: (uint32 [n, 3 D], D), three MSB-first words per data symbol -- the layout
+    of ofdm_receive_stream's d_bits and of ofdm_transmit_packets' d_words.  Every text (str, latin-1, or bytes) is
+    padded with ' ' to D whole symbols of 12 characters (Data_Generator, OFDM.c:435-465); D is n_data, or the largest
+    number of symbols any text needs (at least 1).  ValueError for a text that needs more than 15 symbols or more
+    than n_data.  fileio.decode_message of a row's bits gives the padded text back."""
+    rows = [t.encode("latin-1") if isinstance(t, str) else bytes(t) for t in texts]
+    need = [max((8 * len(b) + 95) // 96, 1) for b in rows]
+    for b, k in zip(rows, need):
+        if k > MAX_DATA_SYMBOLS:
+            raise ValueError(f"a text of {len(b)} characters needs {k} data symbols, a packet carries at most "
+                             f"{MAX_DATA_SYMBOLS} ({12 * MAX_DATA_SYMBOLS} characters)")
+    d = max(need, default=1) if n_data is None else int(n_data)
+    if not 1 <= d <= MAX_DATA_SYMBOLS:
+        raise ValueError(f"n_data must be in [1, {MAX_DATA_SYMBOLS}], got {n_data!r}")
+    if need and max(need) > d:
+        raise ValueError(f"a text needs {max(need)} data symbols, n_data is {d}")
+    buf = np.full((len(rows), 12 * d), 0x20, np.uint8)
+    for k, b in enumerate(rows):
+        buf[k, :len(b)] = np.frombuffer(b, np.uint8)
+    return buf.view(">u4").astype(np.uint32), d
+
+
+def transmit_main(argv=None) -> int:
+    """python ofdm_pkg.py transmit: one packet per line of --messages, each behind --gap idle samples (and a closing
+    gap), with per-packet carrier offsets and gains, written as a complex64 .npy recording that
+    `python ofdm_pkg.py stream --in` decodes line for line."""
+    ap = argparse.ArgumentParser(prog="ofdm_pkg.py transmit", description=transmit_main.__doc__)
+    ap.add_argument("--messages", required=True, help="a text file, one packet per line (at most 180 characters)")
+    ap.add_argument("--out", required=True, help="the recording, a .npy file of complex64 samples at 40 MS/s")
+    ap.add_argument("--gap", type=int, default=500, help="idle samples before every packet and after the last")
+    ap.add_argument("--n-data", type=int, default=None, help="data symbols per packet (default: what the longest line needs)")
+    ap.add_argument("--cfo-hz", default=None, help="carrier offsets in Hz, comma separated, cycled over the packets")
+    ap.add_argument("--gain", default=None, help="complex gains, comma separated, cycled, e.g. 1,0.5j,-0.8+0.3j")
+    ap.add_argument("--snr", type=float, default=20.0, help="dB, against the mean power of the packets' samples")
+    ap.add_argument("--noise", default="none", choices=("real", "complex", "none"))
+    ap.add_argument("--taps", default=None, help="multipath FIR over the recording, e.g. 1,0,0.4+0.3j")
+    ap.add_argument("--seed", type=int, default=0x80211A)
+    a = ap.parse_args(argv)
+    if a.gap < 0:
+        raise SystemExit("--gap must not be negative")
+    import torch  # noqa: PLC0415
+    from . import abi  # noqa: PLC0415
+    from .channel import impair_stream, parse_taps  # noqa: PLC0415
+    from .engine import Engine  # noqa: PLC0415
+    texts = [ln for ln in Path(a.messages).read_text(encoding="latin-1").splitlines() if ln]
+    if not texts:
+        raise SystemExit(f"{a.messages}: no lines")
+    words, d = pack_messages(texts, a.n_data)
+    n, plen = len(texts), abi.packet_len(d)
+    cyc = lambda text, conv, dt: None if text is None else np.resize(np.array([conv(t) for t in text.split(",") if t.strip()], dt), n)
+    cfo, gain = cyc(a.cfo_hz, float, np.float32), cyc(a.gain, complex, np.complex64)
+    with Engine(0) as eng:
+        rec = eng.transmit_packets(words, d, pos0=a.gap, stride=plen + a.gap, gains=gain, cfo_hz=cfo,
+                                   n_out=n * (plen + a.gap) + a.gap)
+        if a.noise != "none" or a.taps is not None:
+            gen = torch.Generator(device="cuda")
+            gen.manual_seed(a.seed)
+            power = float((rec.real.double() ** 2 + rec.imag.double() ** 2).sum()) / (n * plen)
+            rec = impair_stream(rec, power, a.snr, taps=None if a.taps is None else parse_taps(a.taps), noise=a.noise,
+                                generator=gen)
+        x = rec.cpu().numpy()
+    np.save(a.out, x)
+    print(f"{n} packets of {d} data symbols ({plen} samples each), {len(x)} samples -> {a.out}", file=sys.stderr)
+    return 0
+
+
 def main(argv=None) -> int:
     """python ofdm_pkg.py stream: decode every packet of a recording (--in rec.npy, complex64) or of a synthetic
     stream; one line per packet and packets.csv under --out."""
@@ -131,5 +202,5 @@ def main(argv=None) -> int:
     return 0
 
 
-__all__ = ["select_packets", "unpack_cross", "first_packet", "synthetic_segments", "main",
-           "THRESHOLD", "FRONT_GAP", "CONFIRM", "PACKET_OFFSET", "LAST_FRONT"]
+__all__ = ["select_packets", "unpack_cross", "first_packet", "synthetic_segments", "main", "pack_messages",
+           "transmit_main", "MAX_DATA_SYMBOLS", "THRESHOLD", "FRONT_GAP", "CONFIRM", "PACKET_OFFSET", "LAST_FRONT"]
