@@ -33,6 +33,7 @@ EVM_Q_SCALE = float(1 << 20)
 K_FFT, K_TX, K_RX, K_FRAME = range(4)
 K_STREAM_DETECT, K_STREAM_SELECT, K_STREAM_DECODE = 4, 5, 6     # OFDM_K_STREAM_* (ofdm_mi355x_stream.h)
 K_TRANSMIT = 7                                                   # OFDM_K_TRANSMIT (ofdm_mi355x_tx.h)
+K_CHANNEL, K_SCORE = 8, 9                                        # OFDM_K_CHANNEL, OFDM_K_SCORE (ofdm_mi355x_channel.h)
 
 # every entry point of the header, with ctypes argument types
 _V = C.c_void_p
@@ -108,6 +109,23 @@ _TX_SIGS = {
 TX_EXPORTS = list(_TX_SIGS)
 TX_ACCUMULATE = 1                  # OFDM_TX_ACCUMULATE, ofdm_tx_opts.flags bit 0
 
+# the extension header include/ofdm_mi355x_channel.h (multipath, carrier offset and Philox noise over a device-resident
+# recording; received records scored against the transmitted packets); the export lists above and ABI_VERSION do not
+# change with it
+CHANNEL_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_channel.h"
+_CHANNEL_SIGS = {
+    "ofdm_impair_stream": (C.c_int, [_V, _V, _V, _V, _V, C.c_int64]),
+    "ofdm_score_packets": (C.c_int, [_V, C.c_int32, _V, C.c_int64, _V, C.c_int64, C.c_int64, _V, _V, _V, C.c_int32,
+                                     C.c_int32, _V, _V]),
+}
+CHANNEL_EXPORTS = tuple(_CHANNEL_SIGS)
+NOISE_REAL, NOISE_COMPLEX, NOISE_NONE = NOISE["real"], NOISE["complex"], NOISE["none"]   # OFDM_NOISE_* (ofdm_mi355x.h)
+CHANNEL_MAX_TAPS = 32              # OFDM_CHANNEL_MAX_TAPS
+CHANNEL_TILE = 1024                # OFDM_CHANNEL_TILE
+NSCORE = 8                         # OFDM_NSCORE
+S_TRANSMITTED, S_MATCHED, S_RECEIVED, S_BITS, S_BIT_ERR, S_PACKET_ERR = range(6)     # the totals row
+SCORE_MAX_WINDOW = 300             # off_hi - off_lo at most
+
 
 class OfdmError(RuntimeError):
     pass
@@ -130,6 +148,24 @@ class RxOpts(C.Structure):
 class TxOpts(C.Structure):
     """ofdm_tx_opts (16 bytes)"""
     _fields_ = [("conv", C.c_int32), ("float_taps", C.c_int32), ("n_data", C.c_int32), ("flags", C.c_int32)]
+
+
+class ChannelOpts(C.Structure):
+    """ofdm_channel_opts (64 bytes)"""
+    _fields_ = [("power", C.c_double), ("snr_db", C.c_double), ("cfo_hz", C.c_double), ("seed", C.c_uint64),
+                ("trial", C.c_uint64), ("index0", C.c_int64), ("noise", C.c_int32), ("snr_index", C.c_int32),
+                ("n_taps", C.c_int32), ("lead", C.c_int32)]
+
+
+class Score(C.Structure):
+    """ofdm_score (8 bytes, one per transmitted packet)"""
+    _fields_ = [("rx_index", C.c_int32), ("bit_err", C.c_int32)]
+
+
+def score_dtype():
+    """numpy structured dtype of ofdm_score"""
+    import numpy as np  # noqa: PLC0415
+    return np.dtype([("rx_index", "<i4"), ("bit_err", "<i4")])
 
 
 class CaptureResult(C.Structure):
@@ -237,7 +273,8 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
         raise OfdmError(f"{p} not found: the HIP library must be built (build_lib.build()); "
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS}.items():
+    for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS,
+                              **_CHANNEL_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -30,9 +30,10 @@ int check_symbol_payload(const Ctx *c, int payload);
 
 struct Ctx {
     // 4..6: the stream receiver's kernels (OFDM_K_STREAM_* of ofdm_mi355x_stream.h), 7: the packet transmitter
-    // (OFDM_K_TRANSMIT of ofdm_mi355x_tx.h), added at the tail
+    // (OFDM_K_TRANSMIT of ofdm_mi355x_tx.h), 8, 9: the channel and the scoring (OFDM_K_CHANNEL, OFDM_K_SCORE of
+    // ofdm_mi355x_channel.h), added at the tail
     enum { K_FFT = 0, K_TX = 1, K_RX = 2, K_FRAME = 3, K_STREAM_DETECT = 4, K_STREAM_SELECT = 5, K_STREAM_DECODE = 6,
-           K_TRANSMIT = 7, NK = 8 };
+           K_TRANSMIT = 7, K_CHANNEL = 8, K_SCORE = 9, NK = 10 };
     int device = 0;
     int cus = 256;
     hipStream_t own = nullptr;       // created by the context

@@ -27,6 +27,7 @@
 #include "ofdm_internal.h"
 #include "ofdm_ctx.h"
 #include "ofdm_rxcommon.h"
+#include "ofdm_phasor.h"
 #include "ofdm_mi355x_tx.h"
 #include <algorithm>
 #include <cmath>
@@ -42,7 +43,6 @@ constexpr int TXP_ZERO = TXP_PRE + TXP_PAD + 320;
 constexpr int TXP_ROWS = TXP_ZERO + TXP_PAD;
 constexpr int TXP_LDS = TXP_ROWS + 64 * TXP_ROW;     // 4,500 complex samples = 36,000 B: four blocks per CU
 constexpr int TXP_BLOCKS_PER_CU = 2;         // resident blocks the launch is sized for (200-210 VGPRs: 2 waves per SIMD)
-constexpr double TXP_TS = 25e-9;             // sample period of the oversampled waveform (OFDM.c:16-17, x2)
 
 // short training tones S_k at bins 6..58 (OFDM.c:483-490), as ofdm_frame.hip
 __host__ __device__ constexpr int txp_stf_sign(int bin) {
@@ -65,12 +65,7 @@ struct TxPkArgs {
 
 // g exp(j 2 pi f m Ts): revolutions in fp64, reduced to [-1/2, 1/2], then the fp32 sine and cosine
 __device__ __forceinline__ float2 txp_phasor(bool has_gain, float2 g, bool has_cfo, double f, int m) {
-    float2 e = make_float2(1.0f, 0.0f);
-    if (has_cfo) {
-        const double rev = f * (double)m * TXP_TS;
-        const float r = (float)(rev - rint(rev));
-        sincospif(2.0f * r, &e.y, &e.x);
-    }
+    const float2 e = has_cfo ? carrier_phasor(f, (double)m) : make_float2(1.0f, 0.0f);
     return has_gain ? cmul(g, e) : e;
 }
 

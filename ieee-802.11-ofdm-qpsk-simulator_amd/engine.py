@@ -2,7 +2,8 @@
 
 Mirrors the reference's three hot-path functions (src/OFDM.c):
     Transmitter()            OFDM.c:467-618   -> Engine.transmitter() / Engine.tx_frames()
-    Transmission_Over_Air()  OFDM.c:635-655   -> Engine.transmission_over_air()
+    Transmission_Over_Air()  OFDM.c:635-655   -> Engine.transmission_over_air() / Engine.impair_stream() (a device
+                                                 recording: multipath, carrier offset, reproducible noise)
     Receiver()               OFDM.c:941-1165  -> Engine.receiver() / Engine.rx_frames() / Engine.receive_captures() /
                                                  Engine.receive_stream() (every packet of one recording)
 and main()'s SNR loop (OFDM.c:1187-1222) -> Engine.symbol_sweep() / Engine.frame_sweep().
@@ -400,7 +401,7 @@ class Engine:
 
     def receive_stream(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
                        want_bits: bool = True, want_eq: bool = False, want_metric: bool = False,
-                       want_cross: bool = False, counters=None) -> dict:
+                       want_cross: bool = False, counters=None, keep_device: bool = False) -> dict:
         """Every packet of one recording of any length (ofdm_receive_stream, include/ofdm_mi355x_stream.h): the
         reference's detection rule once over the whole recording, then the receiver chain on every packet found.
 
@@ -412,7 +413,8 @@ class Engine:
         structured host array, abi.stream_packet_dtype()), bits ([count, 96 D] int32), eq ([count, 48 D] complex64),
         messages, metric (float32 [n - 47]) and cross (uint32 words, stream.unpack_cross) -- those not asked for None;
         bits, eq, metric and cross stay on the device for torch input.  The call reads the packet count back, so it
-        waits for the device."""
+        waits for the device.  keep_device: also return d_packets (uint8 [rows, 64]), d_count (int64 [2]) and d_words
+        (int32 [rows, 3 D], None without want_bits), the device tensors the kernels wrote, for score_packets."""
         torch = _torch()
         opts = make_rx_opts(mode)
         nd = self.payload_frames(payload)
@@ -443,17 +445,8 @@ class Engine:
                     and counters.numel() == abi.NCOUNTERS and counters.is_contiguous()):
                 raise ValueError("counters must be a contiguous int64 device tensor of NCOUNTERS elements")
         lc = max(n - 47, 0)
-        rows = max(max_packets, 1)                                    # a pointer even when nothing may be written
-        pk = torch.empty((rows, C.sizeof(abi.StreamPacket)), dtype=torch.uint8, device=dev)
-        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
-        words = torch.empty((rows, 3 * nd), dtype=torch.int32, device=dev) if want_bits else None
-        eq = torch.empty((rows, 48 * nd), dtype=torch.complex64, device=dev) if want_eq else None
-        metric = torch.empty(max(lc, 1), dtype=torch.float32, device=dev) if want_metric else None
-        cross = torch.empty(max((lc + 31) // 32, 1), dtype=torch.int32, device=dev) if want_cross else None
-        opt = lambda x: None if x is None else _ptr(x)
-        check(self.lib, self.lib.ofdm_receive_stream(
-            self.ctx, _ptr(t) if n else None, n, C.byref(opts), abi.PAYLOAD[payload], max_packets, _ptr(pk), _ptr(cnt),
-            opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream")
+        pk, cnt, words, eq, metric, cross = self._launch_receive_stream(
+            t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross, counters)
         found, count = (int(v) for v in cnt.cpu())
         records = pk[:count].cpu().numpy().view(abi.stream_packet_dtype()).reshape(count)
         bits = None
@@ -473,8 +466,217 @@ class Engine:
             eq = None if eq is None else eq.cpu().numpy()
             metric = None if metric is None else metric.cpu().numpy()
             cross = None if cross is None else cross.cpu().numpy().view(np.uint32)
-        return dict(count=count, found=found, positions=records["packet_pos"].copy(), records=records, bits=bits,
-                    eq=eq, messages=messages, metric=metric, cross=cross, frames=nd)
+        out = dict(count=count, found=found, positions=records["packet_pos"].copy(), records=records, bits=bits,
+                   eq=eq, messages=messages, metric=metric, cross=cross, frames=nd)
+        if keep_device:
+            out.update(d_packets=pk, d_count=cnt, d_words=words)
+        return out
+
+    def receive_stream_device(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
+                              counters=None) -> dict:
+        """receive_stream for a device recording without the read-back: nothing waits for the device.  samples: a
+        one-dimensional contiguous torch complex64 tensor on this engine's device.  Returns d_packets (uint8
+        [rows, 64], ofdm_stream_packet), d_count (int64 [2]: found, written) and d_words (int32 [rows, 3 D]), of which
+        the first d_count[1] rows are written, and frames -- what score_packets takes."""
+        torch = _torch()
+        opts = make_rx_opts(mode)
+        nd = self.payload_frames(payload)
+        dev = torch.device("cuda", self.device)
+        if not torch.is_tensor(samples) or samples.dtype != torch.complex64 or samples.dim() != 1:
+            raise ValueError("samples must be a one-dimensional torch complex64 tensor")
+        if samples.device != dev:
+            raise ValueError(f"samples are on {samples.device}, the engine runs on {dev}")
+        n = int(samples.shape[0])
+        if n > 1 and samples.stride(0) != 1:
+            raise ValueError(f"samples need a unit stride, got {samples.stride(0)}")
+        if max_packets is None:
+            max_packets = n // 301 + 1
+        if int(max_packets) != max_packets or max_packets < 0:
+            raise ValueError(f"max_packets must be a non-negative integer, got {max_packets!r}")
+        pk, cnt, words = self._launch_receive_stream(samples, opts, payload, nd, int(max_packets), True, False, False,
+                                                     False, counters)[:3]
+        return dict(d_packets=pk, d_count=cnt, d_words=words, frames=nd)
+
+    def _launch_receive_stream(self, t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross,
+                               counters):
+        """Allocates ofdm_receive_stream's outputs and enqueues it: (packets, count, words, eq, metric, cross)"""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n = int(t.shape[0])
+        lc = max(n - 47, 0)
+        rows = max(max_packets, 1)                                    # a pointer even when nothing may be written
+        pk = torch.empty((rows, C.sizeof(abi.StreamPacket)), dtype=torch.uint8, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        words = torch.empty((rows, 3 * nd), dtype=torch.int32, device=dev) if want_bits else None
+        eq = torch.empty((rows, 48 * nd), dtype=torch.complex64, device=dev) if want_eq else None
+        metric = torch.empty(max(lc, 1), dtype=torch.float32, device=dev) if want_metric else None
+        cross = torch.empty(max((lc + 31) // 32, 1), dtype=torch.int32, device=dev) if want_cross else None
+        opt = lambda x: None if x is None else _ptr(x)
+        check(self.lib, self.lib.ofdm_receive_stream(
+            self.ctx, _ptr(t) if n else None, n, C.byref(opts), abi.PAYLOAD[payload], max_packets, _ptr(pk), _ptr(cnt),
+            opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream")
+        return pk, cnt, words, eq, metric, cross
+
+    def impair_stream(self, x, power: float, snr_db: float, cfo_hz: float = 0.0, taps=None, noise: str = "real",
+                      seed: int = 0x80211A, trial: int = 0, snr_index: int = 0, index0: int = 0, lead: int = 0,
+                      out=None):
+        """The channel over a device-resident recording (ofdm_impair_stream, include/ofdm_mi355x_channel.h): the
+        multipath FIR `taps` (complex, at most 32), the rotation exp(j 2 pi cfo_hz k 25e-9) by the absolute index
+        k = index0 + i, then noise of variance power / 10^(snr_db / 10) from the Philox stream (seed, trial, snr_index)
+        at index k ("real": all of it in the real part, "complex": split across both axes, "none").
+
+        x: a contiguous one-dimensional torch complex64 tensor on this engine's device, or a numpy complex64 array,
+        uploaded once.  Its first `lead` samples are history for the filter and give no output: the result has
+        len(x) - lead samples.  out: the tensor to write, used in place; `out is x` (lead 0, at most one tap) is the
+        in-place case.  Returns the device tensor.  Anything malformed raises ValueError before any launch; the call
+        does not wait for the device."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        if noise not in abi.NOISE:
+            raise ValueError(f"noise must be one of {tuple(abi.NOISE)}, got {noise!r}")
+        if isinstance(x, np.ndarray):
+            if x.dtype != np.complex64 or x.ndim != 1:
+                raise ValueError(f"x must be complex64 [n], got {x.dtype} {x.shape}")
+            x = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        elif not torch.is_tensor(x):
+            raise ValueError(f"x must be a torch tensor or a numpy array, got {type(x).__name__}")
+        for name, t in (("x", x), ("out", out)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.complex64 or t.dim() != 1:
+                raise ValueError(f"{name} must be a one-dimensional torch complex64 tensor")
+            if t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, the engine runs on {dev}")
+            if t.shape[0] > 1 and t.stride(0) != 1:
+                raise ValueError(f"{name} needs a unit stride, got {t.stride(0)}")
+        for name, v in (("trial", trial), ("seed", seed), ("snr_index", snr_index), ("index0", index0), ("lead", lead)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+        seed, trial, snr_index, index0, lead = int(seed), int(trial), int(snr_index), int(index0), int(lead)
+        if not 0 <= seed < 1 << 64 or not 0 <= trial < 1 << 64:
+            raise ValueError("seed and trial must fit 64 unsigned bits")
+        if not 0 <= snr_index < 1 << 24:
+            raise ValueError(f"snr_index must be in [0, 2^24), got {snr_index}")
+        if index0 < 0 or index0 >= 1 << 62:
+            raise ValueError(f"index0 must be a non-negative stream index, got {index0}")
+        if not 0 <= lead <= int(x.shape[0]):
+            raise ValueError(f"lead must be in [0, len(x) = {int(x.shape[0])}], got {lead}")
+        for name, v in (("power", power), ("snr_db", snr_db), ("cfo_hz", cfo_hz)):
+            if not np.isfinite(float(v)):
+                raise ValueError(f"{name} must be finite, got {v!r}")
+        if float(power) < 0:
+            raise ValueError(f"power must not be negative, got {power!r}")
+        h = np.zeros(0, np.complex64) if taps is None else np.ascontiguousarray(np.asarray(taps).ravel(), np.complex64)
+        if len(h) > abi.CHANNEL_MAX_TAPS:
+            raise ValueError(f"at most {abi.CHANNEL_MAX_TAPS} taps, got {len(h)}")
+        if not np.isfinite(h.view(np.float32)).all():
+            raise ValueError("taps must be finite")
+        n = int(x.shape[0]) - lead
+        if out is None:
+            out = torch.empty(n, dtype=torch.complex64, device=dev)
+        elif int(out.shape[0]) != n:
+            raise ValueError(f"out must hold len(x) - lead = {n} samples, got {int(out.shape[0])}")
+        if noise != "none" and index0 + n > 1 << (34 if noise == "real" else 33):
+            raise ValueError(f"index0 + n = {index0 + n} exceeds the {noise} noise stream's 2^{34 if noise == 'real' else 33} samples")
+        if n:
+            a0, a1 = x.data_ptr(), x.data_ptr() + 8 * (lead + n)
+            b0, b1 = out.data_ptr(), out.data_ptr() + 8 * n
+            if b0 < a1 and a0 < b1 and not (b0 == a0 and lead == 0 and len(h) <= 1):
+                raise ValueError("out overlaps x: in place needs out to start where x starts, lead 0 and at most one tap")
+        opts = abi.ChannelOpts(float(power), float(snr_db), float(cfo_hz), seed, trial, index0, abi.NOISE[noise],
+                               snr_index, len(h), lead)
+        try:
+            check(self.lib, self.lib.ofdm_impair_stream(
+                self.ctx, C.byref(opts), h.ctypes.data_as(C.c_void_p) if len(h) else None, _ptr(x) if n else None,
+                _ptr(out) if n else None, n), "impair_stream")
+        except abi.OfdmError as e:
+            if "(-1)" in str(e):
+                raise ValueError(str(e)) from None
+            raise
+        return out
+
+    def score_packets(self, words, n_data: int, rx, positions=None, pos0: int = 0, stride: int | None = None,
+                      window=(8, 40), totals=None) -> dict:
+        """Scores received records against the transmitted packets on the device (ofdm_score_packets,
+        include/ofdm_mi355x_channel.h; stream.score_packets is the rule in numpy).
+
+        words, positions, pos0, stride: what transmit_packets was given (device tensors used in place, numpy arrays
+        uploaded).  rx: receive_stream's result with keep_device=True, receive_stream_device's result, or the tuple
+        (d_packets, d_count, d_words).  window: (off_lo, off_hi), the offsets packet_pos - position that count as a
+        match.  totals: an int64 device tensor of NSCORE elements, added to; otherwise a zeroed one is made.
+        Returns scores (int32 [n, 2] device tensor: rx_index, bit_err) and totals (the device tensor); nothing waits
+        for the device unless numpy inputs were uploaded."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        if isinstance(n_data, bool) or int(n_data) != n_data or not 1 <= n_data <= abi.LONG_MAX_DATA_SYMBOLS:
+            raise ValueError(f"n_data must be an integer in [1, {abi.LONG_MAX_DATA_SYMBOLS}], got {n_data!r}")
+        n_data = int(n_data)
+        try:
+            lo, hi = (int(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError(f"window must be (off_lo, off_hi), got {window!r}") from None
+        if not (0 <= lo <= hi and hi - lo <= abi.SCORE_MAX_WINDOW):
+            raise ValueError(f"window needs 0 <= off_lo <= off_hi and off_hi - off_lo <= {abi.SCORE_MAX_WINDOW}, got {window!r}")
+        uploaded = False
+
+        def device_array(x, name, np_dtype, torch_dtypes, ndim):
+            nonlocal uploaded
+            if isinstance(x, np.ndarray):
+                if x.dtype != np_dtype or x.ndim != ndim:
+                    raise ValueError(f"{name} must be {np_dtype} with {ndim} dimensions, got {x.dtype} {x.shape}")
+                uploaded = True
+                return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+            if not torch.is_tensor(x) or x.dtype not in torch_dtypes or x.dim() != ndim:
+                raise ValueError(f"{name} must be a torch tensor or a numpy array of {np_dtype} with {ndim} dimensions")
+            if x.device != dev or not x.is_contiguous():
+                raise ValueError(f"{name} must be contiguous on {dev}")
+            return x
+
+        if isinstance(words, np.ndarray) and words.dtype == np.uint32:
+            words = words.view(np.int32)
+        w = device_array(words, "words", np.dtype(np.int32), (torch.int32, getattr(torch, "uint32", torch.int32)), 2)
+        if w.shape[1] != 3 * n_data:
+            raise ValueError(f"words must be uint32 / int32 [n, {3 * n_data}], got {tuple(w.shape)}")
+        n = int(w.shape[0])
+        pos = None
+        if positions is not None:
+            pos = device_array(positions, "positions", np.dtype(np.int64), (torch.int64,), 1)
+            if int(pos.shape[0]) != n:
+                raise ValueError(f"positions must be int64 [n] with n = {n}, got {tuple(pos.shape)}")
+        if stride is None:
+            stride = abi.packet_len(n_data)
+        if int(pos0) != pos0 or int(stride) != stride:
+            raise ValueError(f"pos0 and stride must be integers, got {pos0!r}, {stride!r}")
+        if isinstance(rx, dict):
+            if any(rx.get(k) is None for k in ("d_packets", "d_count", "d_words")):
+                raise ValueError("rx needs d_packets, d_count and d_words: receive_stream(..., keep_device=True)")
+            if rx.get("frames", n_data) != n_data:
+                raise ValueError(f"rx holds packets of {rx['frames']} data symbols, n_data is {n_data}")
+            pk, cnt, rw = rx["d_packets"], rx["d_count"], rx["d_words"]
+        else:
+            try:
+                pk, cnt, rw = rx
+            except (TypeError, ValueError):
+                raise ValueError("rx must be receive_stream's result or (d_packets, d_count, d_words)") from None
+        for name, t, dt in (("d_packets", pk, torch.uint8), ("d_count", cnt, torch.int64), ("d_words", rw, torch.int32)):
+            if not (torch.is_tensor(t) and t.dtype == dt and t.device == dev and t.is_contiguous()):
+                raise ValueError(f"rx {name} must be a contiguous {dt} tensor on {dev}")
+        rows = int(pk.shape[0]) if pk.dim() == 2 else -1
+        if pk.dim() != 2 or pk.shape[1] != C.sizeof(abi.StreamPacket) or cnt.numel() != 2 \
+                or tuple(rw.shape) != (rows, 3 * n_data):
+            raise ValueError(f"rx needs d_packets [rows, 64], d_count [2] and d_words [rows, {3 * n_data}]")
+        if totals is None:
+            totals = torch.zeros(abi.NSCORE, dtype=torch.int64, device=dev)
+        elif not (torch.is_tensor(totals) and totals.dtype == torch.int64 and totals.device == dev
+                  and totals.numel() == abi.NSCORE and totals.is_contiguous()):
+            raise ValueError("totals must be a contiguous int64 device tensor of NSCORE elements")
+        scores = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        check(self.lib, self.lib.ofdm_score_packets(
+            self.ctx, n_data, _ptr(w) if n else None, n, None if pos is None else _ptr(pos), int(pos0), int(stride),
+            _ptr(pk), _ptr(cnt), _ptr(rw), lo, hi, _ptr(scores) if n else None, _ptr(totals)), "score_packets")
+        if uploaded:
+            self.synchronize()
+        return dict(scores=scores, totals=totals)
 
     def word_length_report(self, capture: np.ndarray) -> dict:
         """Word_Optimization_Analysis (OFDM.c:38-73) of the capture's RRC matched-filter output."""

@@ -4,7 +4,8 @@ select_packets() is the executable specification of include/ofdm_mi355x_stream.h
 (OFDM.c:685-771) over a whole recording, reporting every confirmed front instead of the first one.  The kernels
 (csrc/ofdm_stream.hip) are tested against it bit for bit; it is host code for tests and tools and is never on a hot
 path.  main() is `python ofdm_pkg.py stream`.  pack_messages() packs texts into the payload words both the receivers'
-d_bits and ofdm_transmit_packets' d_words use; transmit_main() is `python ofdm_pkg.py transmit`.
+d_bits and ofdm_transmit_packets' d_words use; transmit_main() is `python ofdm_pkg.py transmit`.  score_packets() is
+the executable specification of ofdm_score_packets (include/ofdm_mi355x_channel.h).
 """
 from __future__ import annotations
 
@@ -105,6 +106,44 @@ def pack_messages(texts, n_data: int | None = None):
     return buf.view(">u4").astype(np.uint32), d
 
 
+SCORE_MAX_WINDOW = 300    # off_hi - off_lo at most: fronts are at least 301 apart, so a window holds one record
+NSCORE = 8                # OFDM_NSCORE
+
+
+def score_packets(tx_pos, tx_words, rx_pos, rx_words, window=(8, 40)) -> dict:
+    """The scoring rule of include/ofdm_mi355x_channel.h in numpy, as select_packets is the detection rule:
+    transmitted packet k (position tx_pos[k], payload words tx_words[k]) matches the received record j with the
+    smallest j for which off_lo <= rx_pos[j] - tx_pos[k] <= off_hi (rx_pos ascending); rx_index = j and bit_err = the
+    differing bits of the two rows of words, or -1 and 0 without a match.
+
+    Returns rx_index and bit_err (int32 [n_tx]) and totals (int64 [8]: transmitted, matched, received, bits
+    compared, bit errors, matched packets with at least one bit error, 0, 0)."""
+    lo, hi = (int(v) for v in window)
+    if not (0 <= lo <= hi and hi - lo <= SCORE_MAX_WINDOW):
+        raise ValueError(f"window needs 0 <= off_lo <= off_hi and off_hi - off_lo <= {SCORE_MAX_WINDOW}, got {window!r}")
+    tx_pos = np.asarray(tx_pos, np.int64).reshape(-1)
+    rx_pos = np.asarray(rx_pos, np.int64).reshape(-1)
+    n_tx, n_rx = len(tx_pos), len(rx_pos)
+    tw = np.asarray(tx_words).astype(np.uint32, copy=False)
+    rw = np.asarray(rx_words).astype(np.uint32, copy=False)
+    if tw.ndim != 2 or rw.ndim != 2 or len(tw) != n_tx or len(rw) != n_rx or tw.shape[1] != rw.shape[1]:
+        raise ValueError(f"tx_words [{n_tx}, W] and rx_words [{n_rx}, W] expected, got {tw.shape} and {rw.shape}")
+    if n_rx > 1 and (np.diff(rx_pos) < 0).any():
+        raise ValueError("rx_pos must be ascending")
+    j = np.searchsorted(rx_pos, tx_pos + lo, side="left")               # the first record at or behind pos + off_lo
+    hit = j < n_rx
+    hit[hit] = rx_pos[j[hit]] - tx_pos[hit] <= hi
+    rx_index = np.where(hit, j, -1).astype(np.int32)
+    bit_err = np.zeros(n_tx, np.int32)
+    if hit.any():
+        x = tw[hit] ^ rw[j[hit]]
+        bit_err[hit] = np.unpackbits(np.ascontiguousarray(x).view(np.uint8), axis=1).sum(axis=1)
+    totals = np.zeros(NSCORE, np.int64)
+    totals[:6] = (n_tx, int(hit.sum()), n_rx, 32 * tw.shape[1] * int(hit.sum()), int(bit_err.sum()),
+                  int((bit_err > 0).sum()))
+    return dict(rx_index=rx_index, bit_err=bit_err, totals=totals)
+
+
 def transmit_main(argv=None) -> int:
     """python ofdm_pkg.py transmit: one packet per line of --messages, each behind --gap idle samples (and a closing
     gap), with per-packet carrier offsets and gains, written as a complex64 .npy recording that
@@ -203,4 +242,4 @@ def main(argv=None) -> int:
 
 
 __all__ = ["select_packets", "unpack_cross", "first_packet", "synthetic_segments", "main", "pack_messages",
-           "transmit_main", "MAX_DATA_SYMBOLS", "THRESHOLD", "FRONT_GAP", "CONFIRM", "PACKET_OFFSET", "LAST_FRONT"]
+           "transmit_main", "score_packets", "SCORE_MAX_WINDOW", "NSCORE", "MAX_DATA_SYMBOLS", "THRESHOLD", "FRONT_GAP", "CONFIRM", "PACKET_OFFSET", "LAST_FRONT"]

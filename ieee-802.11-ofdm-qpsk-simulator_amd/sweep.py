@@ -20,6 +20,9 @@ instead.  BER is errors / bits (= the mean per-trial BER: every trial carries th
 Multi-GPU: launched under torchrun, each rank takes a contiguous share of the trials
 (dist.shard_range); reference_main() forms the process group (dist.init_from_env: RCCL, or gloo
 with OFDM_DIST_BACKEND=gloo) and the counters are summed with one all-reduce before rank 0 writes.
+
+link_sweep() / link_main() (`ofdm_pkg.py link`) sweep packets that each carry their own bits: transmitted once,
+then impaired, received and scored per SNR point on the device (include/ofdm_mi355x_channel.h).
 """
 from __future__ import annotations
 
@@ -168,6 +171,113 @@ def captures_main(argv=None):
             print(f"CFO = {f:9.1f} Hz   SNR = {s:5.1f} dB   BER = {b:.3e}   sync fail = {sf:.3f}", file=sys.stderr)
     (out / "ofdm_captures.json").write_text(json.dumps(side, indent=1))
     return c
+
+
+def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: float = 0.0, taps=None,
+               noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=(8, 40)) -> dict:
+    """Packet-error and bit-error counts against SNR for packets that each carry their own bits, the recording never
+    leaving the device: the packets (words: uint32 [n, 3 n_data], each behind `gap` idle samples, and a closing gap)
+    are transmitted once; per SNR point q the clean recording is impaired into a second buffer with the noise stream
+    (seed, trial, q) (Engine.impair_stream), received (Engine.receive_stream_device) and scored
+    (Engine.score_packets, offsets `window`) into row q of a device table that is read once at the end.  The SNR
+    refers to the mean power of the packets' samples.  The context's MESSAGE payload is set to n_data symbols of
+    blanks (the receiver takes its packet length from it).
+
+    Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
+    import torch  # noqa: PLC0415
+    snr = np.atleast_1d(np.asarray(snr_db, np.float64))
+    n, plen = int(len(words)), abi.packet_len(n_data)
+    if gap < 0:
+        raise ValueError(f"gap must not be negative, got {gap}")
+    if gap < window[1]:
+        raise ValueError(f"gap {gap} is shorter than the scoring window {tuple(window)}: a record could serve two packets")
+    set_message(engine, " " * (12 * n_data))
+    dev = torch.device("cuda", engine.device)
+    w = words if torch.is_tensor(words) else torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(dev)
+    n_out = n * (plen + gap) + gap
+    clean = engine.transmit_packets(w, n_data, pos0=gap, stride=plen + gap, n_out=n_out)
+    # mean |w|^2 over the packets' samples: the gaps are zero
+    power = float((clean.real.double() ** 2 + clean.imag.double() ** 2).sum()) / max(n * plen, 1)
+    rec = torch.empty_like(clean)
+    totals = torch.zeros((len(snr), abi.NSCORE), dtype=torch.int64, device=dev)
+    for q, s in enumerate(snr):
+        engine.impair_stream(clean, power, float(s), cfo_hz, taps=taps, noise=noise, seed=seed, trial=trial,
+                             snr_index=q, out=rec)
+        rx = engine.receive_stream_device(rec)
+        engine.score_packets(w, n_data, rx, pos0=gap, stride=plen + gap, window=window, totals=totals[q])
+    return dict(snr_db=snr, totals=totals.cpu().numpy(), power=power, packets=n, samples=n_out)
+
+
+LINK_COLUMNS = ("snr_db", "transmitted", "matched", "missed", "false_alarms", "packet_err", "bit_err", "bits")
+
+
+def parse_snr_grid(text: str) -> np.ndarray:
+    """'LO:HI:STEP' -> LO, LO + STEP, .. up to and including HI; a single number is one point"""
+    parts = [float(t) for t in text.split(":")]
+    if len(parts) == 1:
+        return np.array(parts)
+    if len(parts) != 3 or parts[2] <= 0 or parts[1] < parts[0]:
+        raise ValueError(f"--snr takes LO:HI:STEP with STEP > 0 and HI >= LO, got {text!r}")
+    lo, hi, step = parts
+    return lo + step * np.arange(int(np.floor((hi - lo) / step + 1e-9)) + 1)
+
+
+def link_main(argv=None) -> int:
+    """`ofdm_pkg.py link`: transmit -> channel -> receive -> score per SNR point on the device; writes the reference's
+    Output_SNR.txt and Output_BER.txt (bit errors over bits compared, on matched packets) and link.csv under --out."""
+    import csv  # noqa: PLC0415
+    from .channel import NOISE_KINDS, parse_taps  # noqa: PLC0415
+    from .fileio import write_float_array_to_file  # noqa: PLC0415
+    from .stream import pack_messages  # noqa: PLC0415
+    ap = argparse.ArgumentParser(prog="ofdm_pkg.py link", description=link_main.__doc__)
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--packets", type=int, help="packets of random payload bits (drawn from --seed)")
+    src.add_argument("--messages", help="a text file, one packet per line (at most 180 characters)")
+    ap.add_argument("--n-data", type=int, default=None, help="data symbols per packet (default 2, or what the longest line needs)")
+    ap.add_argument("--gap", type=int, default=500, help="idle samples before every packet and after the last")
+    ap.add_argument("--snr", default="6:40:1", help="SNR grid in dB, LO:HI:STEP")
+    ap.add_argument("--cfo-hz", type=float, default=0.0)
+    ap.add_argument("--taps", default=None, help="multipath FIR at the oversampled rate, e.g. 1,0,0.4+0.3j")
+    ap.add_argument("--noise", choices=list(NOISE_KINDS), default="real")
+    ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x80211A)
+    ap.add_argument("--out", default="data")
+    a = ap.parse_args(argv)
+    snr = parse_snr_grid(a.snr)
+    if a.messages:
+        texts = [ln for ln in Path(a.messages).read_text(encoding="latin-1").splitlines() if ln]
+        if not texts:
+            raise SystemExit(f"{a.messages}: no lines")
+        words, d = pack_messages(texts, a.n_data)
+    else:
+        if a.packets < 0:
+            raise SystemExit("--packets must not be negative")
+        d = 2 if a.n_data is None else a.n_data
+        if not 1 <= d <= abi.LONG_MAX_DATA_SYMBOLS:
+            raise SystemExit(f"--n-data must be in [1, {abi.LONG_MAX_DATA_SYMBOLS}]")
+        words = np.random.default_rng(a.seed).integers(0, 1 << 32, (a.packets, 3 * d), dtype=np.uint64).astype(np.uint32)
+    out = Path(a.out)
+    out.mkdir(parents=True, exist_ok=True)
+    t0 = time.perf_counter()
+    with Engine(0) as eng:
+        res = link_sweep(eng, words, d, a.gap, snr, cfo_hz=a.cfo_hz, taps=None if a.taps is None else parse_taps(a.taps),
+                         noise=a.noise, seed=a.seed)
+    wall = time.perf_counter() - t0
+    t = res["totals"]
+    ber = t[:, abi.S_BIT_ERR] / np.maximum(t[:, abi.S_BITS], 1)
+    write_float_array_to_file(snr, out / "Output_SNR.txt")
+    write_float_array_to_file(ber, out / "Output_BER.txt")
+    with open(out / "link.csv", "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(LINK_COLUMNS)
+        for s, r in zip(snr, t):
+            tx, matched, received = int(r[abi.S_TRANSMITTED]), int(r[abi.S_MATCHED]), int(r[abi.S_RECEIVED])
+            wr.writerow([f"{s:g}", tx, matched, tx - matched, received - matched, int(r[abi.S_PACKET_ERR]),
+                         int(r[abi.S_BIT_ERR]), int(r[abi.S_BITS])])
+            print(f"SNR = {s:5.1f} dB   matched {matched}/{tx}   false alarms {received - matched}   "
+                  f"BER = {r[abi.S_BIT_ERR] / max(int(r[abi.S_BITS]), 1):.3e}", file=sys.stderr)
+    print(f"{res['packets']} packets of {d} data symbols, {res['samples']} samples, {len(snr)} SNR points in {wall:.2f} s "
+          f"-> {out / 'link.csv'}", file=sys.stderr)
+    return 0
 
 
 def main(argv=None):

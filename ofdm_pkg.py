@@ -35,6 +35,7 @@ if __name__ == "__main__":
     # python ofdm_pkg.py captures [args...]   BER / EVM under CFO, multipath, complex noise (ofdm_amd.sweep.captures_main)
     # python ofdm_pkg.py stream [args...]     every packet of a recording or a synthetic stream (ofdm_amd.stream.main)
     # python ofdm_pkg.py transmit [args...]   one packet per line of a text file into a recording (ofdm_amd.stream.transmit_main)
+    # python ofdm_pkg.py link [args...]       packet and bit errors against SNR, all on the device (ofdm_amd.sweep.link_main)
     cmd = sys.argv[1] if len(sys.argv) > 1 else "build"
     if cmd == "sweep":
         load()
@@ -52,5 +53,9 @@ if __name__ == "__main__":
         load()
         from ofdm_amd import stream  # noqa: PLC0415
         raise SystemExit(stream.transmit_main(sys.argv[2:]))
+    elif cmd == "link":
+        load()
+        from ofdm_amd import sweep  # noqa: PLC0415
+        raise SystemExit(sweep.link_main(sys.argv[2:]))
     else:
         print(build(force="--force" in sys.argv))
