@@ -734,7 +734,20 @@ void launch_rx(hipStream_t st, const RxArgs &a, const ofdm_cfg &cfg, bool dump, 
     }
 }
 
-int rx_grid(const ofdm_cfg &cfg, int64_t n_frames, int device) {
+// Test switch: OFDM_RX_GRID_CAP = n >= 1 limits a receiver launch to n blocks (read on every call; unset, empty,
+// not a number or < 1: no limit).  Every receiver's item loop is written for any grid of at least one block (the
+// device-dependent limit below is as arbitrary), so a small cap reaches the strided rounds, the packed
+// receiver's split tail and the LS receiver's group queue at a few hundred frames on any device.
+static int grid_cap(int grid) {
+    const char *s = getenv("OFDM_RX_GRID_CAP");
+    if (!s || !*s) return grid;
+    char *end = nullptr;
+    const long long cap = strtoll(s, &end, 10);
+    if (*end || cap < 1) return grid;
+    return cap < grid ? (int)cap : grid;
+}
+
+static int rx_device_grid(const ofdm_cfg &cfg, int64_t n_frames, int device) {
     if (rx_pack_applies(cfg)) return rx_pack_grid(cfg, n_frames, device);
     // LS: one block per 21-frame group in flight; ideal: one wave per 64 symbols, 4 waves per block
     // one block per staged group in flight (LS: 21 frames, ideal: 64 symbols)
@@ -751,6 +764,10 @@ int rx_grid(const ofdm_cfg &cfg, int64_t n_frames, int device) {
     const int64_t cap = (int64_t)per_cu * cus;
     const int64_t g = need < cap ? need : cap;
     return (int)(g < 1 ? 1 : g);
+}
+
+int rx_grid(const ofdm_cfg &cfg, int64_t n_frames, int device) {
+    return grid_cap(rx_device_grid(cfg, n_frames, device));
 }
 
 }  // namespace ofdm

@@ -370,6 +370,7 @@ def test_txrx_equals_tx_then_rx(engine, pkg, kw):
     import torch
     cfg = pkg.make_cfg(**{"est": "ls", "noise": "real", **kw})
     for first, n, snr in ((5, 1000, [0.0, 10.0]), (3006, 333, list(np.arange(0.0, 40.0, 2.0))), (7, 64, [4.0]),
+                          (3006, 333, list(np.linspace(-2.0, 32.5, 70))),      # two launches: 64 + 6 SNR points
                           (11, 40_000, [2.0, 8.0]), (13, 120_000, [2.0, 8.0, 14.0])):
         tx_ref, bits_ref = engine.tx_frames(cfg, first, n)
         want = engine.rx_frames(cfg, tx_ref, bits_ref, first, n, snr).cpu().numpy()
