@@ -34,6 +34,7 @@ K_FFT, K_TX, K_RX, K_FRAME = range(4)
 K_STREAM_DETECT, K_STREAM_SELECT, K_STREAM_DECODE = 4, 5, 6     # OFDM_K_STREAM_* (ofdm_mi355x_stream.h)
 K_TRANSMIT = 7                                                   # OFDM_K_TRANSMIT (ofdm_mi355x_tx.h)
 K_CHANNEL, K_SCORE = 8, 9                                        # OFDM_K_CHANNEL, OFDM_K_SCORE (ofdm_mi355x_channel.h)
+K_FADE, K_DRAW_TAPS = 10, 11                                     # OFDM_K_FADE, OFDM_K_DRAW_TAPS (ofdm_mi355x_fading.h)
 
 # every entry point of the header, with ctypes argument types
 _V = C.c_void_p
@@ -125,6 +126,18 @@ CHANNEL_TILE = 1024                # OFDM_CHANNEL_TILE
 NSCORE = 8                         # OFDM_NSCORE
 S_TRANSMITTED, S_MATCHED, S_RECEIVED, S_BITS, S_BIT_ERR, S_PACKET_ERR = range(6)     # the totals row
 SCORE_MAX_WINDOW = 300             # off_hi - off_lo at most
+
+# the extension header include/ofdm_mi355x_fading.h (a FIR of its own for every transmitted packet, and Rayleigh taps
+# drawn on the device); the export lists above and ABI_VERSION do not change with it
+FADING_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_fading.h"
+_FADING_SIGS = {
+    "ofdm_faded_len": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "ofdm_draw_taps": (C.c_int, [_V, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, _V, _V]),
+    "ofdm_transmit_faded": (C.c_int, [_V, _V, _V, C.c_int64, _V, C.c_int64, C.c_int64, _V, _V, _V, C.c_int32, _V,
+                                      C.c_int64]),
+}
+FADING_EXPORTS = tuple(_FADING_SIGS)
+FADE_MAX_TAPS = 32                 # OFDM_FADE_MAX_TAPS
 
 
 class OfdmError(RuntimeError):
@@ -231,6 +244,11 @@ def packet_len(frames: int) -> int:
     return 2 * (320 + 80 * frames) + 20
 
 
+def faded_len(frames: int, n_taps: int) -> int:
+    """A packet of ofdm_transmit_faded: packet_len(frames) + n_taps - 1 (ofdm_faded_len)."""
+    return packet_len(frames) + n_taps - 1
+
+
 def capture_len(frames: int) -> int:
     """Receiver() capture, int(0.307 x waveform length) (OFDM.c:945): 3008 for D = 2."""
     return int(wave_len(frames) * 0.307)
@@ -274,7 +292,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
     for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS,
-                              **_CHANNEL_SIGS}.items():
+                              **_CHANNEL_SIGS, **_FADING_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

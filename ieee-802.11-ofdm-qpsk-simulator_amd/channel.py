@@ -148,4 +148,34 @@ def parse_taps(text: str) -> np.ndarray:
     return np.array([complex(t.strip()) for t in text.split(",") if t.strip()], np.complex64)
 
 
-__all__ = ["make_captures", "make_stream", "impair_stream", "parse_taps", "TS_OVERSAMPLED"]
+FADE_MAX_TAPS = 32            # OFDM_FADE_MAX_TAPS (include/ofdm_mi355x_fading.h)
+
+
+def parse_pdp(text: str) -> np.ndarray:
+    """'1,0.5,0.25,0.125' -> the power delay profile of Engine.draw_taps: float64 linear powers, one per 25 ns tap,
+    normalised to sum 1.  At most 32 entries, each finite and not negative, not all zero."""
+    try:
+        p = np.array([float(t) for t in text.split(",") if t.strip()], np.float64)
+    except ValueError:
+        raise ValueError(f"a power delay profile is comma-separated linear powers, got {text!r}") from None
+    if not 1 <= len(p) <= FADE_MAX_TAPS:
+        raise ValueError(f"a power delay profile has 1 to {FADE_MAX_TAPS} taps, got {len(p)}")
+    if not np.isfinite(p).all() or (p < 0).any() or p.sum() <= 0:
+        raise ValueError(f"powers must be finite, not negative and not all zero, got {text!r}")
+    return p / p.sum()
+
+
+def fade_packets(packets, taps) -> np.ndarray:
+    """Engine.transmit_faded's rule in numpy fp64 (as stream.select_packets is for detection): packets complex [n, P]
+    and taps complex [n, L] -> complex128 [n, P + L - 1], row k the full convolution of packet k with its taps."""
+    x = np.asarray(packets, np.complex128)
+    h = np.asarray(taps, np.complex128)
+    if x.ndim != 2 or h.ndim != 2 or len(x) != len(h) or h.shape[1] < 1:
+        raise ValueError(f"packets [n, P] and taps [n, L >= 1] are required, got {x.shape} and {h.shape}")
+    out = np.zeros((len(x), x.shape[1] + h.shape[1] - 1), np.complex128)
+    for l in range(h.shape[1]):
+        out[:, l:l + x.shape[1]] += h[:, l, None] * x
+    return out
+
+
+__all__ = ["make_captures", "make_stream", "impair_stream", "parse_taps", "parse_pdp", "fade_packets", "TS_OVERSAMPLED"]

@@ -225,6 +225,12 @@ class Engine:
         furthest packet when positions is a numpy array.  accumulate adds to the recording (fp32 atomic adds) instead
         of storing.  Anything malformed raises ValueError before any launch.  The call waits for the device only when it
         uploaded numpy inputs (their device copies are released on return)."""
+        return self._transmit(words, n_data, None, positions, pos0, stride, gains, cfo_hz, out, n_out, accumulate, conv,
+                              float_taps)
+
+    def _transmit(self, words, n_data, taps, positions, pos0, stride, gains, cfo_hz, out, n_out, accumulate, conv,
+                  float_taps):
+        """transmit_packets (taps None) and transmit_faded: the argument checks and the launch"""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         if int(n_data) != n_data or not 1 <= n_data <= abi.LONG_MAX_DATA_SYMBOLS:
@@ -232,7 +238,6 @@ class Engine:
         n_data = int(n_data)
         if conv not in abi.CONV:
             raise ValueError(f"conv must be one of {tuple(abi.CONV)}, got {conv!r}")
-        plen = abi.packet_len(n_data)
 
         uploaded = []
 
@@ -259,6 +264,14 @@ class Engine:
         if w.shape[1] != 3 * n_data:
             raise ValueError(f"words must be uint32 / int32 [n, {3 * n_data}], got {tuple(w.shape)}")
         n = int(w.shape[0])
+        h, L = None, 1
+        if taps is not None:
+            h = device_array(taps, "taps", (np.dtype(np.complex64),), (torch.complex64,), "complex64 [n, L]", 2)
+            L = int(h.shape[1])
+            if int(h.shape[0]) != n or not 1 <= L <= abi.FADE_MAX_TAPS:
+                raise ValueError(f"taps must be complex64 [n = {n}, L] with 1 <= L <= {abi.FADE_MAX_TAPS}, "
+                                 f"got {tuple(h.shape)}")
+        plen = abi.faded_len(n_data, L)                                   # L = 1: the packet length itself
         per_packet = (("positions", positions, (np.dtype(np.int64),), (torch.int64,), "int64 [n]"),
                       ("gains", gains, (np.dtype(np.complex64),), (torch.complex64,), "complex64 [n]"),
                       ("cfo_hz", cfo_hz, (np.dtype(np.float32),), (torch.float32,), "float32 [n]"))
@@ -296,12 +309,60 @@ class Engine:
         opts = abi.TxOpts(abi.CONV[conv], int(bool(float_taps)), n_data, abi.TX_ACCUMULATE if accumulate else 0)
         opt = lambda x: None if x is None else _ptr(x)
         n_rec = int(rec.shape[0])
-        check(self.lib, self.lib.ofdm_transmit_packets(
-            self.ctx, C.byref(opts), _ptr(w) if n else None, n, opt(dv["positions"]), pos0, stride, opt(dv["gains"]),
-            opt(dv["cfo_hz"]), _ptr(rec) if n_rec else None, n_rec), "transmit_packets")
+        if h is None:
+            check(self.lib, self.lib.ofdm_transmit_packets(
+                self.ctx, C.byref(opts), _ptr(w) if n else None, n, opt(dv["positions"]), pos0, stride, opt(dv["gains"]),
+                opt(dv["cfo_hz"]), _ptr(rec) if n_rec else None, n_rec), "transmit_packets")
+        else:
+            check(self.lib, self.lib.ofdm_transmit_faded(
+                self.ctx, C.byref(opts), _ptr(w) if n else None, n, opt(dv["positions"]), pos0, stride, opt(dv["gains"]),
+                opt(dv["cfo_hz"]), _ptr(h) if n else None, L, _ptr(rec) if n_rec else None, n_rec), "transmit_faded")
         if uploaded:
             self.synchronize()
         return rec
+
+    def draw_taps(self, n: int, pdp, seed: int = 0x80211A, index0: int = 0, out=None):
+        """Rayleigh taps for n packets on the device (ofdm_draw_taps, include/ofdm_mi355x_fading.h): a torch complex64
+        device tensor [n, len(pdp)], tap l of packet k a complex Gaussian of power pdp[l], a function of
+        (seed, index0 + k, l) alone.  pdp: at most 32 finite powers >= 0, used as they are (channel.parse_pdp
+        normalises a text).  out: the tensor to fill, used in place.  Anything malformed raises ValueError before any
+        launch; the call does not wait for the device."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        for name, v in (("n", n), ("seed", seed), ("index0", index0)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+        n, seed, index0 = int(n), int(seed), int(index0)
+        if n < 0:
+            raise ValueError(f"n must not be negative, got {n}")
+        if not 0 <= seed < 1 << 64 or not 0 <= index0 < 1 << 64:
+            raise ValueError("seed and index0 must fit 64 unsigned bits")
+        p = np.ascontiguousarray(np.asarray(pdp, np.float64).ravel(), np.float32)
+        if not 1 <= len(p) <= abi.FADE_MAX_TAPS:
+            raise ValueError(f"pdp must hold 1 to {abi.FADE_MAX_TAPS} powers, got {len(p)}")
+        if not np.isfinite(p).all() or (p < 0).any():
+            raise ValueError("pdp must be finite and not negative")
+        if out is None:
+            out = torch.empty((n, len(p)), dtype=torch.complex64, device=dev)
+        elif not (torch.is_tensor(out) and out.dtype == torch.complex64 and tuple(out.shape) == (n, len(p))
+                  and out.device == dev and out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous torch complex64 tensor [{n}, {len(p)}] on {dev}")
+        check(self.lib, self.lib.ofdm_draw_taps(self.ctx, seed, index0, n, len(p), p.ctypes.data_as(C.c_void_p),
+                                                _ptr(out) if n else None), "draw_taps")
+        return out
+
+    def transmit_faded(self, words, n_data: int, taps, positions=None, pos0: int = 0, stride: int | None = None,
+                       gains=None, cfo_hz=None, out=None, n_out: int | None = None, accumulate: bool = False,
+                       conv: str = "c", float_taps: bool = True):
+        """transmit_packets through a channel of its own per packet (ofdm_transmit_faded,
+        include/ofdm_mi355x_fading.h): packet k is its transmit_packets samples convolved with taps[k] -- complex64
+        [n, L], L at most 32, a torch tensor on this engine's device (Engine.draw_taps) or a numpy array, uploaded -- and
+        then takes its gain and carrier offset; it is abi.faded_len(n_data, L) = P + L - 1 samples long, which is also
+        the default stride.  Every other argument is transmit_packets'."""
+        if taps is None:
+            raise ValueError("taps is required")
+        return self._transmit(words, n_data, taps, positions, pos0, stride, gains, cfo_hz, out, n_out, accumulate, conv,
+                              float_taps)
 
     def transmission_over_air(self, tx: np.ndarray, snr_db: float, seed: int = 0x80211A, trial: int = 0,
                               snr_index: int = 0) -> np.ndarray:

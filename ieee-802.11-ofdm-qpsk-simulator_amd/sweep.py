@@ -174,19 +174,34 @@ def captures_main(argv=None):
 
 
 def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: float = 0.0, taps=None,
-               noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=(8, 40)) -> dict:
+               noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=None, fading=None) -> dict:
     """Packet-error and bit-error counts against SNR for packets that each carry their own bits, the recording never
     leaving the device: the packets (words: uint32 [n, 3 n_data], each behind `gap` idle samples, and a closing gap)
     are transmitted once; per SNR point q the clean recording is impaired into a second buffer with the noise stream
     (seed, trial, q) (Engine.impair_stream), received (Engine.receive_stream_device) and scored
     (Engine.score_packets, offsets `window`) into row q of a device table that is read once at the end.  The SNR
     refers to the mean power of the packets' samples.  The context's MESSAGE payload is set to n_data symbols of
-    blanks (the receiver takes its packet length from it).
+    blanks (the receiver takes its packet length from it).  window defaults to (8, 40).
+
+    fading = dict(pdp=powers, index0=0): every packet goes through Rayleigh taps of its own (Engine.draw_taps with the
+    sweep's seed, drawn once; Engine.transmit_faded), L = len(pdp) taps making it L - 1 samples longer.  The SNR then
+    refers to the realised mean received power per nominal packet sample, sum |clean|^2 / (n P); the default window
+    grows to (8, 40 + L - 1), since the detection front moves with the channel's delay, and `gap` must cover it.  The
+    static taps, cfo_hz and the noise apply afterwards as they do without fading.
 
     Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
     import torch  # noqa: PLC0415
     snr = np.atleast_1d(np.asarray(snr_db, np.float64))
     n, plen = int(len(words)), abi.packet_len(n_data)
+    pdp = None
+    if fading is not None:
+        if set(fading) - {"pdp", "index0"} or "pdp" not in fading:
+            raise ValueError(f"fading is dict(pdp=..., index0=0), got keys {sorted(fading)}")
+        pdp = np.asarray(fading["pdp"], np.float64).ravel()
+        if not 1 <= len(pdp) <= abi.FADE_MAX_TAPS:
+            raise ValueError(f"fading['pdp'] must hold 1 to {abi.FADE_MAX_TAPS} powers, got {len(pdp)}")
+    if window is None:
+        window = (8, 40 + (0 if pdp is None else len(pdp) - 1))
     if gap < 0:
         raise ValueError(f"gap must not be negative, got {gap}")
     if gap < window[1]:
@@ -194,8 +209,15 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     set_message(engine, " " * (12 * n_data))
     dev = torch.device("cuda", engine.device)
     w = words if torch.is_tensor(words) else torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(dev)
-    n_out = n * (plen + gap) + gap
-    clean = engine.transmit_packets(w, n_data, pos0=gap, stride=plen + gap, n_out=n_out)
+    if pdp is None:
+        stride = plen + gap
+        n_out = n * stride + gap
+        clean = engine.transmit_packets(w, n_data, pos0=gap, stride=stride, n_out=n_out)
+    else:
+        stride = abi.faded_len(n_data, len(pdp)) + gap
+        n_out = n * stride + gap
+        h = engine.draw_taps(n, pdp, seed=seed, index0=fading.get("index0", 0))
+        clean = engine.transmit_faded(w, n_data, h, pos0=gap, stride=stride, n_out=n_out)
     # mean |w|^2 over the packets' samples: the gaps are zero
     power = float((clean.real.double() ** 2 + clean.imag.double() ** 2).sum()) / max(n * plen, 1)
     rec = torch.empty_like(clean)
@@ -204,7 +226,7 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
         engine.impair_stream(clean, power, float(s), cfo_hz, taps=taps, noise=noise, seed=seed, trial=trial,
                              snr_index=q, out=rec)
         rx = engine.receive_stream_device(rec)
-        engine.score_packets(w, n_data, rx, pos0=gap, stride=plen + gap, window=window, totals=totals[q])
+        engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])
     return dict(snr_db=snr, totals=totals.cpu().numpy(), power=power, packets=n, samples=n_out)
 
 
@@ -226,7 +248,7 @@ def link_main(argv=None) -> int:
     """`ofdm_pkg.py link`: transmit -> channel -> receive -> score per SNR point on the device; writes the reference's
     Output_SNR.txt and Output_BER.txt (bit errors over bits compared, on matched packets) and link.csv under --out."""
     import csv  # noqa: PLC0415
-    from .channel import NOISE_KINDS, parse_taps  # noqa: PLC0415
+    from .channel import NOISE_KINDS, parse_pdp, parse_taps  # noqa: PLC0415
     from .fileio import write_float_array_to_file  # noqa: PLC0415
     from .stream import pack_messages  # noqa: PLC0415
     ap = argparse.ArgumentParser(prog="ofdm_pkg.py link", description=link_main.__doc__)
@@ -239,10 +261,17 @@ def link_main(argv=None) -> int:
     ap.add_argument("--cfo-hz", type=float, default=0.0)
     ap.add_argument("--taps", default=None, help="multipath FIR at the oversampled rate, e.g. 1,0,0.4+0.3j")
     ap.add_argument("--noise", choices=list(NOISE_KINDS), default="real")
+    ap.add_argument("--fading", choices=["rayleigh"], default=None,
+                    help="a Rayleigh channel of its own for every packet, drawn from --seed (alone: --pdp 1, flat)")
+    ap.add_argument("--pdp", default=None, help="power delay profile of the fading channel: linear powers per 25 ns tap, "
+                                                "e.g. 1,0.5,0.25,0.125 (normalised to sum 1; implies --fading rayleigh)")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x80211A)
     ap.add_argument("--out", default="data")
     a = ap.parse_args(argv)
     snr = parse_snr_grid(a.snr)
+    fading = None
+    if a.fading or a.pdp:
+        fading = dict(pdp=parse_pdp(a.pdp or "1"), index0=0)
     if a.messages:
         texts = [ln for ln in Path(a.messages).read_text(encoding="latin-1").splitlines() if ln]
         if not texts:
@@ -260,7 +289,7 @@ def link_main(argv=None) -> int:
     t0 = time.perf_counter()
     with Engine(0) as eng:
         res = link_sweep(eng, words, d, a.gap, snr, cfo_hz=a.cfo_hz, taps=None if a.taps is None else parse_taps(a.taps),
-                         noise=a.noise, seed=a.seed)
+                         noise=a.noise, seed=a.seed, fading=fading)
     wall = time.perf_counter() - t0
     t = res["totals"]
     ber = t[:, abi.S_BIT_ERR] / np.maximum(t[:, abi.S_BITS], 1)
