@@ -65,6 +65,7 @@ int main(void)
 /* the reference harness's entry points (oracle/ref_harness.c) */
 int ref_init(void);
 int ref_tx_copy(float *out, int max_complex);
+int ref_set_message(const unsigned char *msg, int n);
 void ref_globals(float *bits, float *payload_mod, float *ltf_freq, int *dims);
 void ref_fft(const float *in, float *out, int n);
 void ref_ifft(const float *in, float *out, int n);
@@ -119,6 +120,32 @@ int main(void)
     for (int flags = 0; flags < 8; ++flags) ref_time_symbol_chain(snr, 2, 3, flags, acc5);
     free(tx);
     free(ota);
+    /* a 15-symbol frame from the stage functions: every buffer sized from the new dims, then the default again */
+    unsigned char longmsg[171];
+    for (int i = 0; i < 171; ++i) longmsg[i] = (unsigned char)('a' + i % 26);
+    n = ref_set_message(longmsg, 171);
+    ref_globals(NULL, NULL, NULL, dims);
+    tx = malloc(sizeof(float) * 2 * (size_t)n);
+    ota = malloc(sizeof(float) * 2 * (size_t)n);
+    ref_tx_copy(tx, n);
+    ref_toa(tx, ota, 12.0f, n);
+    {
+        const int nf = dims[0], fsz = dims[1], lr = (int)(n * 0.307);
+        float *c2 = malloc(sizeof(float) * (size_t)lr), *f1 = malloc(sizeof(float) * 2 * (size_t)fsz),
+              *f2 = malloc(sizeof(float) * 2 * (size_t)fsz), *f3 = malloc(sizeof(float) * 2 * (size_t)fsz),
+              *yf = malloc(sizeof(float) * 128 * (size_t)nf), *eq = malloc(sizeof(float) * 96 * (size_t)nf),
+              *bt = malloc(sizeof(float) * 96 * (size_t)nf), *lb = malloc(sizeof(float) * 96 * (size_t)nf);
+        ref_globals(lb, eq, lf, dims);
+        ref_receiver_stages(ota, n, n - lr - 1, c2, f1, f2, f3, H, yf, eq, bt, res, ints);
+        free(c2); free(f1); free(f2); free(f3); free(yf); free(eq); free(bt); free(lb);
+    }
+    ref_trial(10.0f, res);
+    ref_mc_trials(8.0f, 2, acc8);
+    ref_time_symbol_chain(snr, 2, 2, 1, acc5);
+    free(tx);
+    free(ota);
+    ref_set_message((const unsigned char *)"Hey! I am Vivaswan", 18);
+    ref_trial(10.0f, res);
     printf("drive_ref done\n");
     return 0;
 }

@@ -58,6 +58,19 @@ void orc_gauss4(const uint32_t ctr[4], const uint32_t key[2], double z[4])
 #define STREAM_NOISE  0x5A000000u
 #define STREAM_CHAN   0xC4A00000u
 #define STREAM_START  0x5B000000u
+#define STREAM_FIXTURE 0xF1000000u   /* counter word 3 of test-fixture noise (orc_gauss_fill's callers): no sweep uses it */
+
+/* n standard normals for test fixtures: block b = 0, 1, .. has the counter (b, ctr_hi[0], ctr_hi[1], ctr_hi[2]) and
+ * gives out[4b .. 4b+3] in orc_gauss4's order; the caller puts STREAM_FIXTURE (or its own tag) into ctr_hi[2]. */
+void orc_gauss_fill(const uint32_t ctr_hi[3], const uint32_t key[2], int n, double *out)
+{
+    for (int b = 0; 4 * b < n; ++b) {
+        const uint32_t ctr[4] = { (uint32_t)b, ctr_hi[0], ctr_hi[1], ctr_hi[2] };
+        double z[4];
+        orc_gauss4(ctr, key, z);
+        for (int i = 0; i < 4 && 4 * b + i < n; ++i) out[4 * b + i] = z[i];
+    }
+}
 
 static void key_of(uint64_t seed, uint32_t key[2]) { key[0] = (uint32_t)seed; key[1] = (uint32_t)(seed >> 32); }
 

@@ -52,6 +52,9 @@ typedef struct {
 void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 /* four standard normals of one Philox block; u1/u2 quantised exactly as the HIP path */
 void orc_gauss4(const uint32_t ctr[4], const uint32_t key[2], double z[4]);
+/* n normals of the blocks (b, ctr_hi[0..2]), b = 0, 1, ..: reproducible noise for test fixtures (stream tag 0xF1000000
+ * in ctr_hi[2], used by no sweep) */
+void orc_gauss_fill(const uint32_t ctr_hi[3], const uint32_t key[2], int n, double *out);
 
 /* ---- transforms: OFDM.c:314-339 ---- */
 void orc_fft64(const double *in, double *out);              /* fft(): fftshift(DFT(x)) */

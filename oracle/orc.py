@@ -34,7 +34,24 @@ def build_ref() -> Path | None:
     if not os.path.exists(REF_SRC):
         return REF_SO if REF_SO.exists() else None
     subprocess.run(["make", "-s", "ref", f"REF_SRC={REF_SRC}"], cwd=ORACLE_DIR, check=True)
+    # make goes by file times: a library that arrived later than the sources (copied in, restored from a cache) but was
+    # built from an older harness counts as up to date.  Go by what it exports instead, and build it again.
+    if not ref_exports(REF_SO, HARNESS_ENTRIES):
+        subprocess.run(["make", "-s", "-B", "ref", f"REF_SRC={REF_SRC}"], cwd=ORACLE_DIR, check=True)
     return REF_SO
+
+
+# entries of oracle/ref_harness.c that an older build of the library lacks (RefLib.set_message needs them)
+HARNESS_ENTRIES = (b"ref_set_message", b"ref_tx_main_copy")
+
+
+def ref_exports(path: Path, names) -> bool:
+    """The library file names every entry of `names` (read as bytes: nothing is loaded)."""
+    try:
+        blob = Path(path).read_bytes()
+    except OSError:
+        return False
+    return all(n + b"\0" in blob for n in names)
 
 
 def _p(a: np.ndarray | None):
@@ -90,6 +107,7 @@ class Oracle:
         L.orc_word_length.restype = C.c_int
         L.orc_word_length.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.orc_set_message.argtypes = [C.c_char_p, C.c_int]
+        L.orc_gauss_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         self._frames = 2
 
     def word_length(self, capture: np.ndarray, float_taps: bool = True):
@@ -128,6 +146,17 @@ class Oracle:
     def gauss4(self, ctr, key) -> np.ndarray:
         c = np.asarray(ctr, np.uint32); k = np.asarray(key, np.uint32); o = np.zeros(4, np.float64)
         self.lib.orc_gauss4(_p(c), _p(k), _p(o))
+        return o
+
+    FIXTURE_TAG = 0xF1000000          # STREAM_FIXTURE of ofdm_oracle.c: no sweep, channel or start stream uses it
+
+    def gauss_fill(self, ctr_hi, key, n: int) -> np.ndarray:
+        """n standard normals of the Philox blocks (b, ctr_hi[0], ctr_hi[1], ctr_hi[2]), b = 0, 1, ..: four per block
+        in orc_gauss4's order.  Fixture noise (tests/golden/gen_golden.py --only long) is drawn with
+        ctr_hi[2] = FIXTURE_TAG."""
+        c = np.asarray(ctr_hi, np.uint32); k = np.asarray(key, np.uint32); o = np.zeros(int(n), np.float64)
+        assert c.shape == (3,) and k.shape == (2,)
+        self.lib.orc_gauss_fill(_p(c), _p(k), int(n), _p(o))
         return o
 
     def fft64(self, x: np.ndarray) -> np.ndarray:
@@ -229,6 +258,8 @@ class Oracle:
 class RefLib:
     """The unmodified reference OFDM.c behind oracle/ref_harness.c (hooks: main, rand)."""
 
+    DEFAULT_MESSAGE = b"Hey! I am Vivaswan"                             # message[] of OFDM.c:20
+
     def __init__(self, path: Path | None = None):
         path = Path(path or REF_SO)
         if not path.exists():
@@ -236,6 +267,13 @@ class RefLib:
         self.lib = C.CDLL(str(path))
         L = self.lib
         L.ref_init.restype = C.c_int
+        # a library built from an older harness (where the reference's source is not at hand to build it again) still
+        # serves everything but set_message: the frame then stays the compiled-in message's
+        self.has_set_message = all(hasattr(L, n.decode()) for n in HARNESS_ENTRIES)
+        if self.has_set_message:
+            L.ref_set_message.restype = C.c_int
+            L.ref_set_message.argtypes = [C.c_char_p, C.c_int]
+            L.ref_tx_main_copy.restype = C.c_int
         L.ref_time_trials.restype = C.c_double
         L.ref_time_trials.argtypes = [C.c_float, C.c_int, C.c_void_p]
         L.ref_mc_trials.restype = C.c_double
@@ -252,12 +290,42 @@ class RefLib:
         self.n = L.ref_init()
 
     def waveform(self) -> np.ndarray:
+        self.n = self.lib.ref_init()                                  # the current frame's length (set_message)
         o = np.zeros(2 * self.n, np.float32)
         self.lib.ref_tx_copy(_p(o), self.n)
         return o.view(np.complex64).copy()
 
+    def set_message(self, msg: bytes) -> int:
+        """The frame of another message, built from the reference's own stage functions (ref_harness.c
+        ref_set_message); every later call -- waveform, globals, receiver, receiver_stages, the trial loops -- uses
+        it.  Returns the waveform length.  DEFAULT_MESSAGE restores Transmitter()'s own frame bit for bit."""
+        msg = bytes(msg)
+        if not self.has_set_message:
+            raise RuntimeError("this build of the reference library has no ref_set_message: build it again from "
+                               "oracle/ref_harness.c (oracle/Makefile 'ref', where the reference's source exists)")
+        n = self.lib.ref_set_message(msg, len(msg))
+        if n < 0:
+            raise ValueError("message must not be empty")
+        self.n = n
+        return n
+
+    def transmitter_waveform(self) -> np.ndarray:
+        """Transmitter()'s own output for the compiled-in message, whatever set_message did since."""
+        if not self.has_set_message:                                # nothing can have replaced it
+            return self.waveform()
+        o = np.zeros(2 * 9800, np.float32)
+        n = self.lib.ref_tx_main_copy(_p(o), 9800)
+        return o[:2 * n].view(np.complex64).copy()
+
+    def dims(self) -> np.ndarray:
+        """[data_frames_number, Data_Frame_Size, len_Tx_Signal_repeated, 0] of the current frame"""
+        dims = np.zeros(4, np.int32)
+        self.lib.ref_globals(None, None, None, _p(dims))
+        return dims
+
     def globals(self):
-        bits = np.zeros(192, np.float32); pm = np.zeros(192, np.float32); lf = np.zeros(128, np.float32)
+        nf = int(self.dims()[0])
+        bits = np.zeros(96 * nf, np.float32); pm = np.zeros(96 * nf, np.float32); lf = np.zeros(128, np.float32)
         dims = np.zeros(4, np.int32)
         self.lib.ref_globals(_p(bits), _p(pm), _p(lf), _p(dims))
         return dict(bits=bits.astype(np.int32), payload_mod=pm.view(np.complex64).copy(),
@@ -294,9 +362,10 @@ class RefLib:
 
     def receiver_stages(self, ota: np.ndarray, rx_start: int):
         ota = np.ascontiguousarray(ota, np.complex64)
-        nf = 2
-        d = dict(corr=np.zeros(2961, np.float32), rxframe=np.zeros(480, np.complex64),
-                 coarse=np.zeros(480, np.complex64), fine=np.zeros(480, np.complex64),
+        nf, fsz = (int(v) for v in self.dims()[:2])
+        lc = int(len(ota) * 0.307) - 47                                   # len_Corr_Out of the capture (OFDM.c:945, 661)
+        d = dict(corr=np.zeros(lc, np.float32), rxframe=np.zeros(fsz, np.complex64),
+                 coarse=np.zeros(fsz, np.complex64), fine=np.zeros(fsz, np.complex64),
                  H=np.zeros(64, np.complex64), Yf=np.zeros(64 * nf, np.complex64),
                  nopilot=np.zeros(48 * nf, np.complex64), bits=np.zeros(96 * nf, np.float32),
                  res=np.zeros(3, np.float32), ints=np.zeros(4, np.int32))

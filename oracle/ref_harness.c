@@ -65,16 +65,106 @@ static void quiet_end(void)
 }
 
 /* ------------------------------------------------------------------ transmitter (once) */
-static float complex *g_tx = NULL;
+static float complex *g_tx = NULL;      /* the current frame's waveform: every ref_* entry below reads this one */
+static float complex *g_tx_main = NULL; /* Transmitter()'s own output for message[] (OFDM.c:20), kept for comparison */
+static int g_tx_main_len = 0;
 
 /* Transmitter() mutates globals and leaks on re-entry (OFDM.c:467-618): call it exactly once. */
 int ref_init(void)
 {
     if (!g_tx) {
         quiet_begin();
-        g_tx = Transmitter();
+        g_tx_main = g_tx = Transmitter();
+        g_tx_main_len = len_Tx_Signal_repeated;
         quiet_end();
     }
+    return len_Tx_Signal_repeated;
+}
+
+/* Transmitter()'s own waveform of the compiled-in message, whatever ref_set_message did since. */
+int ref_tx_main_copy(float *out, int max_complex)
+{
+    ref_init();
+    int n = g_tx_main_len < max_complex ? g_tx_main_len : max_complex;
+    memcpy(out, g_tx_main, (size_t)n * sizeof(float complex));
+    return n;
+}
+
+/*
+ * The frame of another message (the message is a compile-time array in OFDM.c:20 and Transmitter() cannot run
+ * twice), built from the reference's own stage functions in the order Transmitter() calls them: characters to bits
+ * (Decimal_To_Binary, blanks up to a whole symbol), QPSK_Modulator, the subcarrier map with the four pilots
+ * (Slice_Repeater), ifft, cyclic prefix, the two preambles (Preamble_Generator over the IEEE 802.11a short and long
+ * training tones, as oracle/ofdm_oracle.c preamble_tones states them), 2x zero-stuffing, Convolution with
+ * RRC_Filter_Tx, ten periods.  The globals Receiver() reads -- Data, Data_Payload_Mod, data_frames_number,
+ * Data_Frame_Size, len_Tx_Signal_repeated -- and g_tx are replaced, so ref_trial / ref_time_trials / ref_mc_trials /
+ * ref_receiver / ref_receiver_stages / ref_tx_copy / ref_globals / ref_init all see the new frame.  For the compiled-in
+ * message the result equals Transmitter()'s output bit for bit (tests/test_ref_long.py).  Returns the new
+ * len_Tx_Signal_repeated, or -1 for an empty message.
+ */
+int ref_set_message(const unsigned char *msg, int n)
+{
+    if (!msg || n < 1) return -1;
+    ref_init();
+    quiet_begin();
+    if (Data_Payload_Mod) Deallocate_Array_2D(Data_Payload_Mod, data_frames_number);
+    free(Data);
+    if (g_tx != g_tx_main) free(g_tx);
+
+    const int nf = (int)ceil(8 * n / 96.0);
+    data_frames_number = nf;
+    Data = Allocate_Array_1D(nf * 96);
+    int eight[8];
+    for (int c = 0; c < nf * 12; ++c) {
+        Decimal_To_Binary(c < n ? msg[c] : ' ', eight);
+        for (int b = 0; b < 8; ++b) Data[c * 8 + b] = eight[b];
+    }
+    float complex **payload = Allocate_Array_2D(nf, 96);
+    for (int d = 0; d < nf; ++d) Slice_Repeater(Data, payload[d], 0, 96 * d, 96 * d + 96, 1);
+    Data_Payload_Mod = Allocate_Array_2D(nf, 48);
+    QPSK_Modulator(payload, Data_Payload_Mod, nf);
+    Deallocate_Array_2D(payload, nf);
+
+    static const signed char s_pat[53] = {0,0,1,0,0,0,-1,0,0,0,1,0,0,0,-1,0,0,0,-1,0,0,0,1,0,0,0,0,0,0,0,
+                                           -1,0,0,0,-1,0,0,0,1,0,0,0,1,0,0,0,1,0,0,0,1,0,0};
+    static const signed char l_pat[53] = {1,1,-1,-1,1,1,-1,1,-1,1,1,1,1,1,1,-1,-1,1,1,-1,1,-1,1,1,1,1,0,
+                                           1,-1,-1,1,1,-1,1,-1,1,-1,-1,-1,-1,-1,1,1,-1,-1,1,-1,1,-1,1,1,1,1};
+    /* 54 entries: Preamble_Generator copies P_k[0..54) (OFDM.c:381) and overwrites the last with a guard tone */
+    float complex tones_s[54] = {0}, tones_l[54] = {0}, guard[11] = {0}, stf[160], ltf[160];
+    for (int i = 0; i < 53; ++i) { tones_s[i] = s_pat[i] * (1 + 1 * I); tones_l[i] = l_pat[i]; }
+    float scale = sqrt(13.0 / 6.0);
+    Preamble_Generator(scale, tones_s, guard, stf, 0);
+    Preamble_Generator(1, tones_l, guard, ltf, 1);          /* also rewrites Long_preamble_slot_Frequency: same values */
+
+    Data_Frame_Size = nf * 80 + 320;
+    float complex *frame = Allocate_Array_1D(Data_Frame_Size);
+    Slice_Repeater(stf, frame, 0, 0, 160, 1);
+    Slice_Repeater(ltf, frame, 160, 0, 160, 1);
+    const int pilot[4] = {1, 1, 1, -1};
+    for (int d = 0; d < nf; ++d) {
+        float complex X[N_FFT] = {0}, x[N_FFT];
+        float complex *q = Data_Payload_Mod[d];
+        Slice_Repeater(q, X, 6, 0, 5, 1);    X[11] = pilot[0];
+        Slice_Repeater(q, X, 12, 5, 18, 1);  X[25] = pilot[1];
+        Slice_Repeater(q, X, 26, 18, 24, 1);
+        Slice_Repeater(q, X, 33, 24, 30, 1); X[39] = pilot[2];
+        Slice_Repeater(q, X, 40, 30, 43, 1); X[53] = pilot[3];
+        Slice_Repeater(q, X, 54, 43, 48, 1);
+        ifft(X, x, N_FFT);
+        Slice_Repeater(x, frame, 320 + 80 * d, 48, 64, 1);
+        Slice_Repeater(x, frame, 336 + 80 * d, 0, 64, 1);
+    }
+    const int n_over = 2 * Data_Frame_Size, n_period = n_over + len_RRC_Coeff - 1;
+    float complex *over = Allocate_Array_1D(n_over);
+    for (int i = 0; i < Data_Frame_Size; ++i) { over[2 * i] = frame[i]; over[2 * i + 1] = 0; }
+    free(frame);
+    float complex *period = Convolution(over, RRC_Filter_Tx, n_over, len_RRC_Coeff);
+    free(over);
+    len_Tx_Signal_repeated = 10 * n_period;
+    g_tx = Allocate_Array_1D(len_Tx_Signal_repeated);
+    Slice_Repeater(period, g_tx, 0, 0, n_period, 10);
+    free(period);
+    quiet_end();
     return len_Tx_Signal_repeated;
 }
 
@@ -86,8 +176,9 @@ int ref_tx_copy(float *out, int max_complex)
     return n;
 }
 
-/* Data (OFDM.c:28, 192 bits as float complex), Data_Payload_Mod (OFDM.c:30, 2x48),
- * Long_preamble_slot_Frequency (OFDM.c:34), data_frames_number, Data_Frame_Size. */
+/* Data (OFDM.c:28, 96 bits per data symbol as float complex), Data_Payload_Mod (OFDM.c:30, 48 per data symbol),
+ * Long_preamble_slot_Frequency (OFDM.c:34), data_frames_number, Data_Frame_Size: the caller sizes bits and
+ * payload_mod for the current frame (dims alone first). */
 void ref_globals(float *bits, float *payload_mod, float *ltf_freq, int *dims)
 {
     ref_init();
@@ -238,9 +329,9 @@ double ref_mc_trials(float snr_db, int n_trials, double *acc8)
  * functions, so the result must equal ref_receiver() bit for bit (tested).  The capture offset
  * is passed in instead of drawn (OFDM.c:949).  Any output pointer may be NULL.
  *   corr      [len_corr]      real part of Corr_Out (OFDM.c:972)
- *   rx_frame  [480*2]         down-sampled frame (OFDM.c:992-996)
- *   coarse    [480*2]         after coarse CFO (OFDM.c:1004)
- *   fine      [480*2]         after fine CFO (OFDM.c:1012)
+ *   rx_frame  [fsz*2]         down-sampled frame (OFDM.c:992-996), fsz = Data_Frame_Size (480 for 2 symbols)
+ *   coarse    [fsz*2]         after coarse CFO (OFDM.c:1004)
+ *   fine      [fsz*2]         after fine CFO (OFDM.c:1012)
  *   H         [64*2]          channel estimate (OFDM.c:1020)
  *   Yf        [nf*64*2]       data FFT outputs (OFDM.c:1039)
  *   nopilot   [nf*48*2]       equalised data subcarriers (OFDM.c:1059-1069)
@@ -425,12 +516,13 @@ double ref_time_symbol_chain(const float *snr_db, int n_snr, int n_frames, int f
     ref_init();
     const int rayleigh = flags & 1, ideal = (flags >> 1) & 1;
     const int D = data_frames_number;     /* 2 for the reference message (OFDM.c:439) */
+    const int FR = 320 + 80 * D;          /* symbol-rate frame: 480 for it, more after ref_set_message */
     const int pilot[4] = {1, 1, 1, -1};
     float complex T[64], ltf[64];
     memcpy(ltf, Long_preamble_slot_Frequency, sizeof(ltf));
     ifft(ltf, T, 64);                                      /* long training symbol, C ifft (D5) */
     float complex **payload = Allocate_Array_2D(D, 96), **mod = Allocate_Array_2D(D, 48);
-    float complex frame_tx[480], frame_rx[480], H[64];
+    float complex frame_tx[FR], frame_rx[FR], H[64];
     float complex **rx_time = Allocate_Array_2D(D, 64), **rx_freq = Allocate_Array_2D(D, 64);
     float complex **no_pilot = Allocate_Array_2D(D, 48), **final = Allocate_Array_2D(D, 48);
     float complex **demod = Allocate_Array_2D(D, 96);
@@ -461,15 +553,15 @@ double ref_time_symbol_chain(const float *snr_db, int n_snr, int n_frames, int f
             Slice_Repeater(x, frame_tx, 336 + 80 * d, 0, 64, 1);
         }
         if (rayleigh) {          /* y[n] = sum_l h_l x[n - l], taps CN(0, 1/4) (Box-Muller on rand()) */
-            float complex h[4], y[480];
+            float complex h[4], y[FR];
             for (int l = 0; l < 4; ++l) h[l] = 0.5f * (gaussian_noise(0, 0.5f) + I * gaussian_noise(0, 0.5f));
-            for (int n = 0; n < 480; ++n) {
+            for (int n = 0; n < FR; ++n) {
                 y[n] = 0;
                 for (int l = 0; l < 4 && l <= n; ++l) y[n] += h[l] * frame_tx[n - l];
             }
             memcpy(frame_tx, y, sizeof(y));
         }
-        if (ideal) Channel_Estimation(frame_tx, H, 480);     /* known channel: noiseless LTF pair */
+        if (ideal) Channel_Estimation(frame_tx, H, FR);     /* known channel: noiseless LTF pair */
         for (int q = 0; q < n_snr; ++q) {
             const float kappa = 0.4980f;
             const float sd = sqrtf(kappa * 52.0f / 4096.0f / powf(10.0f, snr_db[q] / 10.0f));
@@ -477,7 +569,7 @@ double ref_time_symbol_chain(const float *snr_db, int n_snr, int n_frames, int f
             for (int i = 192; i < 320; ++i) frame_rx[i] += sd * gaussian_noise(0, 1);
             for (int d = 0; d < D; ++d)
                 for (int i = 336 + 80 * d; i < 400 + 80 * d; ++i) frame_rx[i] += sd * gaussian_noise(0, 1);
-            if (!ideal) Channel_Estimation(frame_rx, H, 480);
+            if (!ideal) Channel_Estimation(frame_rx, H, FR);
             for (int d = 0; d < D; ++d) {
                 Slice_Repeater(frame_rx, rx_time[d], 0, 336 + 80 * d, 400 + 80 * d, 1);
                 fft(rx_time[d], rx_freq[d], 64);

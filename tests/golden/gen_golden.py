@@ -4,6 +4,7 @@ unmodified /root/reference/src/OFDM.c) and from the reference's own data files.
 
 Run in the build container (the GPU box has no /root/reference):
     python tests/golden/gen_golden.py [--only mc] [--mc-trials 48000 --mc-deep-trials 1000000]
+    python tests/golden/gen_golden.py --only long [--procs 8]      (the four ref_long_* / ref_mc_curve_long files only)
 
 Outputs (all plain data, loadable with numpy allow_pickle=False / json):
   fft_vectors.npz      200 random 64-pt inputs and the reference's fft()/ifft() outputs (OFDM.c:314-339)
@@ -19,6 +20,16 @@ Outputs (all plain data, loadable with numpy allow_pickle=False / json):
   ref_symbol_chain_curve.json  the same chain entirely from the reference's stage functions and its
                        gaussian_noise, 0..30 dB step 2, 2e6 frames at 8 / 10 dB and 1e7 at 12 dB (>= 1,000 bit
                        errors each) with per-frame error statistics (frame-clustered BER variance)
+Frames of 1, 3, 5, 8, 9, 13 and 15 data symbols (--only long; RefLib.set_message builds the frame from the reference's
+own stage functions, Receiver() then runs unmodified):
+  ref_long_tx.npz      per frame size: the message, one period of the waveform (the ten are asserted identical), Data
+                       bits, Data_Payload_Mod, dims
+  ref_long_stages.npz  per frame size 8 injected-noise captures through Receiver(): packet_idx, H, equalised carriers,
+                       bits, Res.  No noise is stored: a capture is rebuilt from (frames, case, rs, sigma, seed) by the
+                       rule in the file's `rule` entry (Philox Gaussians of the oracle, stream tag 0xF1000000)
+  ref_long_bulk.npz    1,000 captures each at 1, 8 and 15 symbols: packet_idx, bit errors, carriers near the slicer
+                       threshold, and whether the sync decision sits on Packet_Selection's 0.75 threshold
+  ref_mc_curve_long.json  ref_mc_curve.json's rows for 8 and 15 symbols: 20,000 trials at 6, 8, 10, 12, 14, 20 dB
 """
 from __future__ import annotations
 
@@ -217,14 +228,14 @@ def mc_jobs(trials: int, procs: int, deep_trials: int, deep_snrs=MC_DEEP_SNRS):
     return jobs
 
 
-def gen_mc(trials: int, procs: int, deep_trials: int):
-    jobs = mc_jobs(trials, procs, deep_trials)
-    jobs.sort(key=lambda j: -j[1])                      # long jobs first
-    with mp.Pool(procs) as pool:
-        res = list(pool.imap_unordered(_mc_worker, jobs, chunksize=1))
+MC_KEYS = ("sum_evm_db", "sum_evm_agc_db", "sum_ber", "sum_ber2", "trials_ber_pos", "trials_ber_ge_quarter",
+           "sum_evm_db2", "trials_evm_agc_finite")
+
+
+def mc_rows(res) -> list:
+    """fixture rows from (snr, trials, seconds, acc8) job results"""
     curve = {}
-    keys = ("sum_evm_db", "sum_evm_agc_db", "sum_ber", "sum_ber2", "trials_ber_pos", "trials_ber_ge_quarter",
-            "sum_evm_db2", "trials_evm_agc_finite")
+    keys = MC_KEYS
     for snr, n, t, acc in res:
         c = curve.setdefault(snr, {"trials": 0, "sec": 0.0, **{k: 0.0 for k in keys}})
         c["trials"] += n
@@ -245,6 +256,15 @@ def gen_mc(trials: int, procs: int, deep_trials: int):
                      "mean_evm_agc_db": c["sum_evm_agc_db"] / n,
                      "trials_evm_agc_finite": int(c["trials_evm_agc_finite"]),
                      "sec_per_trial": c["sec"] / n})
+    return rows
+
+
+def gen_mc(trials: int, procs: int, deep_trials: int):
+    jobs = mc_jobs(trials, procs, deep_trials)
+    jobs.sort(key=lambda j: -j[1])                      # long jobs first
+    with mp.Pool(procs) as pool:
+        res = list(pool.imap_unordered(_mc_worker, jobs, chunksize=1))
+    rows = mc_rows(res)
     meta = {"generator": f"tests/golden/gen_golden.py --only mc --mc-trials {trials} --procs {procs} "
                          f"--mc-deep-trials {deep_trials}",
             "source": "reference OFDM.c (gcc -O2) TOA+Receiver loop (ref_harness.c ref_mc_trials)",
@@ -256,6 +276,235 @@ def gen_mc(trials: int, procs: int, deep_trials: int):
     (HERE / "ref_mc_curve.json").write_text(json.dumps(meta, indent=1))
 
 
+# ---------------------------------------------------------------- frames of 1 and 3..15 data symbols (--only long)
+# Messages, typed in as data.  15 symbols: the reference's own second text (the commented alternative of OFDM.c:21, 171
+# characters).  The other sizes: tests/test_gpu_long_frames.py's text cut as its text(n) cuts it (n - 1 characters and a
+# full stop, so that no message ends in the blank the decoder strips) at 12, 30, 55, 96, 97 and 150 characters.
+REF_LONG_MESSAGE = (b"The Supreme Lord Shree Krishna said: I taught this eternal science of Yog to the Sun God, Vivasvan, "
+                    b"who passed it on to Manu; and Manu, in turn, instructed it to Ikshvaku.")
+LONG_TEXT = (b"Long frames on the MI355X: the capture no longer fits one wave's share of the LDS, so the sync kernel keeps a "
+             b"ring of it and detects a round at a time; fifteen data symbols is the cap!!")
+LONG_CHARS = {1: 12, 3: 30, 5: 55, 8: 96, 9: 97, 13: 150, 15: 171}
+LONG_D = tuple(LONG_CHARS)
+FIXTURE_TAG = 0xF1000000                   # Philox counter word 3 of fixture noise (oracle/ofdm_oracle.c STREAM_FIXTURE)
+STAGE_SNRS = (100.0, 30.0, 20.0, 14.0, 12.0, 10.0, 8.0, 6.0)
+BULK_D = (1, 8, 15)
+BULK_N = 1000
+BULK_SNRS = (6.0, 8.0, 10.0, 12.0, 16.0, 25.0)
+BULK_KEY = (0xB01C, 1)                     # Philox key of the bulk captures; a stages case has the key (seed, 0)
+LONG_MC_D = (8, 15)
+LONG_MC_SNRS = (6.0, 8.0, 10.0, 12.0, 14.0, 20.0)
+LONG_MC_TRIALS = 20_000
+LONG_MC_JOB = 2_500                        # trials per job, seeded by job index: the file does not depend on --procs
+CAPTURE_RULE = ("capture = complex64(wave[rs:rs+L] + float32(sigma * z)), wave = the D-symbol period x 10 (complex64), "
+                "L = int(0.307 * len(wave)), sigma a double, z = oracle.gauss_fill([case, D, 0xF1000000], key, L): the "
+                "doubles of orc_gauss4 over the Philox blocks (b, case, D, 0xF1000000), b = 0, 1, .. -- real-only noise "
+                "on the captured window.  key = (seed, 0) for a stages case; (0xB01C, 1) for a bulk capture, whose `case` is "
+                "its index + 1000 x the noise draws that sat on the sync threshold before it.")
+
+
+def long_message(nd: int) -> bytes:
+    if nd == 15:
+        assert len(REF_LONG_MESSAGE) == 171
+        return REF_LONG_MESSAGE
+    return LONG_TEXT[:LONG_CHARS[nd] - 1] + b"."
+
+
+def long_capture(O, wave: np.ndarray, nd: int, case: int, rs: int, sigma: float, key) -> np.ndarray:
+    """CAPTURE_RULE; `wave` is the complex64 waveform of ten periods."""
+    L = int(len(wave) * 0.307)
+    z = O.gauss_fill([case, nd, FIXTURE_TAG], key, L)
+    return (wave[rs:rs + L] + (sigma * z).astype(np.float32)).astype(np.complex64)
+
+
+def ref_long_decode(R: RefLib, wave: np.ndarray, cap: np.ndarray, rs: int) -> dict:
+    """The reference's Receiver() on a capture laid at rs of the otherwise clean waveform (it reads nothing else)."""
+    ota = wave.copy()
+    ota[rs:rs + len(cap)] = cap
+    return R.receiver_stages(ota, rs)
+
+
+def threshold_decisions(corr: np.ndarray) -> set:
+    """conftest.off_threshold_pidx_mismatches' rule: Packet_Selection's decisions with the 0.75 threshold moved by up to
+    +-0.1 % in 21 steps (tests/test_lazy_rule.packet_selection, pinned to the compiled reference)."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    from test_lazy_rule import packet_selection  # noqa: PLC0415
+    return {packet_selection(corr, 0.75 * (1 + d)) for d in np.linspace(-1e-3, 1e-3, 21)}
+
+
+def near_threshold(nopilot: np.ndarray) -> int:
+    """components of the equalised carriers within 1e-4 of the slicer threshold (a decision there may differ)"""
+    return int(np.sum(np.abs(nopilot.real) < 1e-4) + np.sum(np.abs(nopilot.imag) < 1e-4))
+
+
+def stage_starts(n: int, L: int) -> list:
+    """eight capture starts: both ends, the middle, one capture straddling a period boundary in its first quarter"""
+    per = n // 10
+    return [0, n - L - 1, (n - L) // 2, 3 * per - L // 4, 1234, per + 17, 5 * per - 1, (n - L) // 3]
+
+
+def stages_case(R: RefLib, O, wave, P, nd: int, case: int, snr: float, rs: int, seed: int):
+    """one ref_long_stages case, or None when a generator condition fails (the caller tries the next seed)"""
+    sigma = float(np.sqrt(P / 10 ** (snr / 10)))
+    cap = long_capture(O, wave, nd, case, rs, sigma, (seed, 0))
+    d = ref_long_decode(R, wave, cap, rs)
+    ota = wave.copy()
+    ota[rs:rs + len(cap)] = cap
+    rr = R.receiver(ota, rs)
+    if not np.array_equal(np.nan_to_num(rr, neginf=-999), np.nan_to_num(d["res"], neginf=-999)):
+        raise AssertionError(("Receiver() and receiver_stages differ", nd, case, rr, d["res"]))    # condition 1
+    if d["ints"][3] != 0:                                                                           # condition 2
+        return None
+    if threshold_decisions(d["corr"]) != {d["packet_idx"]}:                                         # condition 3
+        return None
+    return dict(packet_idx=np.int32(d["packet_idx"]), H=d["H"], nopilot=d["nopilot"], bits=d["bits"].astype(np.int8),
+                res=d["res"], ints=d["ints"], sigma=np.float64(sigma), rs=np.int32(rs), snr=np.float64(snr),
+                seed=np.int64(seed))
+
+
+def gen_long_tx(R: RefLib) -> dict:
+    out, waves = {}, {}
+    for nd in LONG_D:
+        msg = long_message(nd)
+        n = R.set_message(msg)
+        g = R.globals()
+        w = R.waveform()
+        assert int(g["dims"][0]) == nd and n == len(w) == 10 * (2 * (320 + 80 * nd) + 20), (nd, n, g["dims"])
+        per = w.reshape(10, -1)
+        assert all(np.array_equal(per[k].view(np.uint32), per[0].view(np.uint32)) for k in range(10))
+        out.update({f"d{nd}_msg": np.frombuffer(msg, np.uint8), f"d{nd}_period": per[0].copy(),
+                    f"d{nd}_bits": g["bits"].astype(np.int8), f"d{nd}_payload_mod": g["payload_mod"],
+                    f"d{nd}_dims": g["dims"]})
+        waves[nd] = w
+    np.savez_compressed(HERE / "ref_long_tx.npz", frames=np.array(LONG_D, np.int32), **out)
+    return waves
+
+
+def gen_long_stages(R: RefLib, O, waves: dict):
+    out = {}
+    for nd in LONG_D:
+        R.set_message(long_message(nd))
+        w = waves[nd]
+        truth = R.globals()["bits"]
+        P = float(np.mean(np.abs(w.astype(np.complex128)) ** 2))
+        L = int(len(w) * 0.307)
+        cases = []
+        for case, (snr, rs) in enumerate(zip(STAGE_SNRS, stage_starts(len(w), L))):
+            # condition 4 for every frame size: when no earlier case lost sync, the last (6 dB) one is one that does
+            want_fail = case == len(STAGE_SNRS) - 1 and all(int(c["packet_idx"]) != 0 for c in cases)
+            for seed in range(1000 * nd + 100 * case + 1, 1000 * nd + 100 * case + 100):
+                c = stages_case(R, O, w, P, nd, case, snr, rs, seed)
+                if c is not None and (not want_fail or int(c["packet_idx"]) == 0):
+                    break
+            else:
+                raise AssertionError(("no seed gives a usable case", nd, case))
+            cases.append(c)
+        fails = sum(int(c["packet_idx"]) == 0 for c in cases)
+        clean = sum(int(c["packet_idx"]) != 0 and np.array_equal(c["bits"], truth) for c in cases)
+        assert fails > 0 and clean > 0, (nd, fails, clean)                                          # condition 4
+        print(f"stages D={nd}: {fails} sync failures, {clean} error-free decodes, seeds {[int(c['seed']) for c in cases]}")
+        for k in cases[0]:
+            out[f"d{nd}_{k}"] = np.array([c[k] for c in cases])
+    np.savez_compressed(HERE / "ref_long_stages.npz", frames=np.array(LONG_D, np.int32), rule=np.array(CAPTURE_RULE),
+                        **out)
+
+
+BULK_DRAWS = 3         # noise draws tried per bulk capture (see bulk_capture_row)
+
+
+def bulk_capture_row(R: RefLib, O, wave, truth, nd: int, k: int, rs: int, sigma: float):
+    """One bulk capture: (case, packet_idx, bit errors, near, on_threshold, draws on the threshold).  By the +-0.1 % rule
+    about 4 % of uniformly drawn captures sit on Packet_Selection's threshold at every SNR (the metric climbs the
+    plateau's edge by ~1/64 per sample, so 0.1 % of 0.75 moves the first crossing by a sample in that share of them);
+    such a capture gets another noise draw, as a stages case gets another seed: case = k + BULK_N x draw, recorded."""
+    moved = 0
+    for draw in range(BULK_DRAWS):
+        case = k + BULK_N * draw
+        cap = long_capture(O, wave, nd, case, rs, sigma, BULK_KEY)
+        d = ref_long_decode(R, wave, cap, rs)
+        assert d["ints"][3] == 0, ("late frame read past the buffer", nd, case)
+        on = len(threshold_decisions(d["corr"])) > 1
+        if not on:
+            break
+        moved += 1
+    return case, d["packet_idx"], int(np.sum(d["bits"] != truth)), near_threshold(d["nopilot"]), on, moved
+
+
+def gen_long_bulk(R: RefLib, O, waves: dict):
+    out = {}
+    for nd in BULK_D:
+        R.set_message(long_message(nd))
+        w = waves[nd]
+        truth = R.globals()["bits"]
+        P = float(np.mean(np.abs(w.astype(np.complex128)) ** 2))
+        L = int(len(w) * 0.307)
+        rng = np.random.default_rng(802110 + nd)
+        snr = rng.choice(BULK_SNRS, BULK_N)
+        rs = rng.integers(0, len(w) - L, BULK_N).astype(np.int32)
+        sigma = np.sqrt(P / 10 ** (snr / 10))
+        rows = [bulk_capture_row(R, O, w, truth, nd, k, int(rs[k]), float(sigma[k])) for k in range(BULK_N)]
+        case, pidx, err, near, on, moved = (np.array(v) for v in zip(*rows))
+        print(f"bulk D={nd}: {int(np.sum(pidx == 0))} sync failures, {int(np.sum(on))} on the threshold "
+              f"({int(np.sum(moved))} draws on it replaced), {int(np.sum(err == 0))} error-free, "
+              f"{int(np.sum(near > 0))} with a carrier near the slicer threshold")
+        assert np.sum(on) <= 0.005 * BULK_N, (nd, int(np.sum(on)))
+        out.update({f"d{nd}_snr": snr, f"d{nd}_rs": rs, f"d{nd}_sigma": sigma, f"d{nd}_case": case.astype(np.int32),
+                    f"d{nd}_packet_idx": pidx.astype(np.int32), f"d{nd}_bit_err": err.astype(np.int32),
+                    f"d{nd}_near": near.astype(np.int16), f"d{nd}_on_threshold": on.astype(np.bool_)})
+    np.savez_compressed(HERE / "ref_long_bulk.npz", frames=np.array(BULK_D, np.int32), rule=np.array(CAPTURE_RULE),
+                        **out)
+
+
+def _long_mc_worker(args):
+    nd, snr, n, seed = args
+    R = RefLib()
+    R.set_message(long_message(nd))
+    t, acc = R.mc_trials(snr, n, seed)
+    return nd, snr, n, t, acc.tolist()
+
+
+def long_mc_jobs(frames=LONG_MC_D, snrs=LONG_MC_SNRS, trials: int = LONG_MC_TRIALS) -> list:
+    return [(nd, snr, LONG_MC_JOB, 3000029 * (j + 1) + 1000 * nd + int(snr))
+            for nd in frames for snr in snrs for j in range(trials // LONG_MC_JOB)]
+
+
+def gen_long_mc(procs: int):
+    """ref_mc_curve_long.json: ref_mc_trials (Transmission_Over_Air + Receiver, OFDM.c:1206-1217) after set_message"""
+    with mp.Pool(procs) as pool:
+        res = pool.map(_long_mc_worker, long_mc_jobs(), chunksize=1)      # job order: sums independent of --procs
+    rows = []
+    for nd in LONG_MC_D:
+        rows += [{"frames": nd, **r} for r in mc_rows([r[1:] for r in res if r[0] == nd])]
+    meta = {"generator": f"tests/golden/gen_golden.py --only long (jobs of {LONG_MC_JOB} trials)",
+            "source": "reference OFDM.c (gcc -O2) TOA+Receiver loop (ref_harness.c ref_mc_trials) on the frame "
+                      "ref_set_message builds from the reference's stage functions",
+            "rand": "64-bit LCG hook (oracle/ref_harness.c)",
+            "messages": {str(nd): long_message(nd).decode() for nd in LONG_MC_D},
+            "seeds": "job j of a point: 3000029 (j + 1) + 1000 frames + snr",
+            "rows": rows}
+    (HERE / "ref_mc_curve_long.json").write_text(json.dumps(meta, indent=1))
+
+
+def gen_long(R: RefLib, procs: int, parts=("tx", "stages", "bulk", "mc")):
+    from oracle import Oracle  # noqa: PLC0415  (only its Philox Gaussians: the noise rule needs no reference)
+    O = Oracle()
+    try:
+        waves = gen_long_tx(R) if "tx" in parts else None
+        if waves is None:
+            waves = {}
+            for nd in LONG_D:
+                R.set_message(long_message(nd))
+                waves[nd] = R.waveform()
+        if "stages" in parts:
+            gen_long_stages(R, O, waves)
+        if "bulk" in parts:
+            gen_long_bulk(R, O, waves)
+    finally:
+        R.set_message(R.DEFAULT_MESSAGE)
+    if "mc" in parts:
+        gen_long_mc(procs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     # the defaults reproduce the committed ref_mc_curve.json (48000 trials/point, 1e6 at 11, 12 dB, 4e6 at 13, 14, 15)
@@ -263,7 +512,8 @@ def main():
     ap.add_argument("--mc-deep-trials", type=int, default=1_000_000)
     ap.add_argument("--procs", type=int, default=8)
     ap.add_argument("--skip-mc", action="store_true")
-    ap.add_argument("--only", choices=["genie", "mc", "chain"], help="regenerate one fixture only")
+    ap.add_argument("--only", choices=["genie", "mc", "chain", "long"], help="regenerate one fixture only")
+    ap.add_argument("--long-parts", default="tx,stages,bulk,mc", help="--only long: which of its four files to write")
     a = ap.parse_args()
     build_ref()
     R = RefLib()
@@ -275,6 +525,9 @@ def main():
         return
     if a.only == "chain":
         gen_chain(a.procs)
+        return
+    if a.only == "long":
+        gen_long(R, a.procs, tuple(a.long_parts.split(",")))
         return
     gen_fft(R); gen_tx(R); gen_rx(R); gen_kat(); gen_genie(R); gen_chain(a.procs)
     if not a.skip_mc:
