@@ -208,7 +208,9 @@ def stream_packet_dtype():
 
 
 def reduce_capture_records(rec, frames: int):
-    """The counters row ofdm_receive_captures adds for these records (the header's rule): int64 [NCOUNTERS]."""
+    """The counters row ofdm_receive_captures adds for these records (the header's rule): int64 [NCOUNTERS].  A
+    non-finite evm_pre_sum (the long training symbols themselves past the capture's end: Z = 0 / 0) is left out of
+    EVM_PRE_Q and EVMDB_PRE_Q together with its evm_db_pre, as a -inf evm_db_post is left out of EVMDB_POST_Q."""
     import numpy as np  # noqa: PLC0415
     rec = np.asarray(rec)
     out = np.zeros(NCOUNTERS, np.int64)
@@ -220,8 +222,9 @@ def reduce_capture_records(rec, frames: int):
     out[C_OOB] = int((rec["flags"] & CAPTURE_OOB != 0).sum())
     out[C_EVM_POST_AXIS] = rec["post_axis_err"].astype(np.int64).sum()
     q = lambda v: np.rint(v.astype(np.float64) * EVM_Q_SCALE).astype(np.int64)    # llrint of the stored fp32 value
-    out[C_EVM_PRE_Q] = q(rec["evm_pre_sum"]).sum()
-    out[C_EVMDB_PRE_Q] = q(rec["evm_db_pre"]).sum()
+    pre = np.isfinite(rec["evm_pre_sum"])
+    out[C_EVM_PRE_Q] = q(rec["evm_pre_sum"][pre]).sum()
+    out[C_EVMDB_PRE_Q] = q(rec["evm_db_pre"][pre]).sum()
     fin = np.isfinite(rec["evm_db_post"])
     out[C_EVMDB_POST_Q] = q(rec["evm_db_post"][fin]).sum()
     out[C_EVMDB_POST_FINITE] = int(fin.sum())
@@ -254,14 +257,24 @@ def capture_len(frames: int) -> int:
     return int(wave_len(frames) * 0.307)
 
 
-def make_rx_opts(mode: str = "c", fixed_start: int = -1) -> RxOpts:
+RX_OPT_FIELDS = ("cap_len", "float_cfo", "matlab_slicer", "float_taps")
+
+
+def make_rx_opts(mode: str = "c", fixed_start: int = -1, opts: dict | None = None) -> RxOpts:
     """mode 'c': OFDM.c receiver (capture int(0.307 len), 3008 for the reference message; fp32 CFO,
-    fp32 taps); 'matlab': IEEE_802_11_a_Code_Tester.m (capture 3000, MATLAB slicer, double taps)."""
+    fp32 taps); 'matlab': IEEE_802_11_a_Code_Tester.m (capture 3000, MATLAB slicer, double taps).
+    opts: single fields of ofdm_rx_opts (RX_OPT_FIELDS) set over the mode's, e.g. {"cap_len": 1100}."""
     if mode == "c":
-        return RxOpts(0, 1, 0, 1, fixed_start)
-    if mode == "matlab":
-        return RxOpts(3000, 0, 1, 0, fixed_start)
-    raise ValueError(mode)
+        o = RxOpts(0, 1, 0, 1, fixed_start)
+    elif mode == "matlab":
+        o = RxOpts(3000, 0, 1, 0, fixed_start)
+    else:
+        raise ValueError(mode)
+    for k, v in (opts or {}).items():
+        if k not in RX_OPT_FIELDS or isinstance(v, float) or int(v) != v:
+            raise ValueError(f"opts takes integer values for {RX_OPT_FIELDS}, got {k!r}: {v!r}")
+        setattr(o, k, int(v))
+    return o
 
 
 _LIB = None

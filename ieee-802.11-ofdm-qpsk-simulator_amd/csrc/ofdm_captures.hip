@@ -57,7 +57,23 @@ struct CapArgs {
     int32_t fr_sep;          // 1: fr[] has an area of its own (captures too short to hold it beside the filter's reads)
     float taps[21];
     uint32_t dtable[4 * CAPRX_MAX_DATA];   // demap words of the payload (ofdm_rxcommon.h demap_words)
+    uint32_t ztable[CAPRX_MAX_DATA];       // per data symbol, were it all zeros: bit errors | slicer axis errors << 16 (caprx_zero_errors)
 };
+
+// The errors of a data symbol that arrives as 64 exact zeros (its window lies wholly past the capture's end): the
+// reference's slicer decides "-" on both axes for a zero (Z > 0 fails, OFDM.c:858-866), the demapper then (1, 0) for
+// every pair (OFDM.c:873-908), so the counts depend on the payload alone.  w: the symbol's 96 payload bits, MSB first.
+// An axis is wrong where the truth is "+": re > 0 iff b0 == b1, im > 0 iff b0 == 0 (D10).
+static uint32_t caprx_zero_errors(const uint32_t w[3]) {
+    uint32_t be = 0u, ax = 0u;
+    for (int k = 0; k < 3; ++k) be += (uint32_t)__builtin_popcount(w[k] ^ 0xAAAAAAAAu);
+    for (int m = 0; m < 48; ++m) {
+        const uint32_t b0 = (w[(2 * m) >> 5] >> (31 - ((2 * m) & 31))) & 1u;
+        const uint32_t b1 = (w[(2 * m + 1) >> 5] >> (31 - ((2 * m + 1) & 31))) & 1u;
+        ax += (uint32_t)(b0 == b1) + (uint32_t)(b0 == 0u);
+    }
+    return be | (ax << 16);
+}
 
 // LDS ordering between the lanes of one wave (the block's other waves run other captures)
 __device__ __forceinline__ void caprx_wave_sync() {
@@ -192,6 +208,8 @@ __global__ __launch_bounds__(64 * CAPRX_MAX_WAVES) void capture_rx_kernel(CapArg
             else { fre = re + hi + 1; fim = im + hi + 1; }           // hi + 1 + nfr <= plane (host: cap_len >= 4 nfr + 20)
         }
         const bool oob = p + 2 * (nfr - 1) >= L + 20;                // the reference reads past its buffer
+        // the first data symbol wholly past the end: the least d >= 0 with p + 2 (336 + 80 d) >= L + 20; D when none
+        const int zfirst = min(max((L - 652 - p + 159) / 160, 0), nd);
         for (int ii = lane; ii < nfr; ii += 64) {
             if (!caprx_needed(ii)) continue;
             const int n = p + 2 * ii;
@@ -326,6 +344,12 @@ __global__ __launch_bounds__(64 * CAPRX_MAX_WAVES) void capture_rx_kernel(CapArg
             }
         }
         // ---- the capture's totals in symbol order, its record and its counter terms ----
+        // A data symbol whose window lies wholly past the capture's end (sample p + 2 (336 + 80 d) and all after it are
+        // at L + 20 or beyond) reached the demapper as 64 exact zeros: Y = +-0 and u = +-0, and the sign bit of u, which
+        // demap_sub counts, is then an accident of S.  The reference decides "-" on both axes for a zero, as the output
+        // pass above does, so that symbol's counts are the payload's own (ztable).  Those symbols are zfirst .. D - 1
+        // (none unless oob); the branch is wave-uniform and rare, and it stands here, after the transforms (a branch
+        // inside them costs 60 spilled VGPRs).  Its EVM term needs nothing: u' = +-0 gives |0 - d|^2 either way.
         const float fev = dlane ? finish_evm<2>(st) : 0.f;
         const uint32_t bev = dlane ? st.be : 0u, axv = dlane ? st.ax : 0u;
         float fe = 0.f;
@@ -336,9 +360,19 @@ __global__ __launch_bounds__(64 * CAPRX_MAX_WAVES) void capture_rx_kernel(CapArg
             ferr += (uint32_t)__shfl((int)bev, src, 64);
             fax += (uint32_t)__shfl((int)axv, src, 64);
         }
+        if (zfirst < nd) {
+            for (int d = zfirst; d < nd; ++d) {
+                const int src = 4 * (d / 3) + 1 + d % 3;
+                const uint32_t z = a.ztable[d];
+                ferr += (z & 0xffffu) - (uint32_t)__shfl((int)bev, src, 64);
+                fax += (z >> 16) - (uint32_t)__shfl((int)axv, src, 64);
+            }
+        }
         if (lane == 0) {
             const float N = 48.0f * (float)nd;
-            const float db = fe > 0.f ? fmaxf(3.01029995663981195214f * __builtin_amdgcn_logf(fe / N), -400.f) : -400.f;
+            // a NaN sum (the long training symbols themselves past the end: S = 0, Z = 0 / 0) stays NaN, as the reference's
+            const float db = fe > 0.f ? fmaxf(3.01029995663981195214f * __builtin_amdgcn_logf(fe / N), -400.f)
+                                      : (fe == fe ? -400.f : fe);
             const float dbp = fax > 0u ? 3.01029995663981195214f * __builtin_amdgcn_logf(2.0f * (float)fax / N) : -INFINITY;
             ofdm_capture_result *r = a.res + i;
             r->bit_err = (int32_t)ferr;
@@ -356,8 +390,10 @@ __global__ __launch_bounds__(64 * CAPRX_MAX_WAVES) void capture_rx_kernel(CapArg
                 atomicAdd(&acc[OFDM_C_BIT_ERR], (unsigned long long)ferr);
                 atomicAdd(&acc[OFDM_C_FRAME_ERR], (unsigned long long)(ferr > 0u));
                 atomicAdd(&acc[OFDM_C_EVM_POST_AXIS], (unsigned long long)fax);
-                atomicAdd(&acc[OFDM_C_EVM_PRE_Q], (unsigned long long)__float2ll_rn(fe * Q));
-                atomicAdd(&acc[OFDM_C_EVMDB_PRE_Q], (unsigned long long)__float2ll_rn(db * Q));
+                if (fabsf(fe) < INFINITY) {                          // a non-finite term is left out, never converted
+                    atomicAdd(&acc[OFDM_C_EVM_PRE_Q], (unsigned long long)__float2ll_rn(fe * Q));
+                    atomicAdd(&acc[OFDM_C_EVMDB_PRE_Q], (unsigned long long)__float2ll_rn(db * Q));
+                }
                 if (fax > 0u) {
                     atomicAdd(&acc[OFDM_C_EVMDB_POST_Q], (unsigned long long)__float2ll_rn(dbp * Q));
                     atomicAdd(&acc[OFDM_C_EVMDB_POST_FINITE], 1ull);
@@ -410,7 +446,10 @@ extern "C" int ofdm_receive_captures(ofdm_ctx *ctx, const void *d_captures, int6
     CapArgs a{};
     uint32_t table[3 * LONG_MAX_FRAMES];
     a.n_data = payload_table_long(payload, c->message, table);
-    for (int d = 0; d < a.n_data; ++d) demap_words(table + 3 * d, a.dtable + 4 * d);
+    for (int d = 0; d < a.n_data; ++d) {
+        demap_words(table + 3 * d, a.dtable + 4 * d);
+        a.ztable[d] = caprx_zero_errors(table + 3 * d);
+    }
     const int nfr = 320 + 80 * a.n_data;
     const int L = opts->cap_len ? opts->cap_len : (int)(10 * (2 * nfr + 20) * 0.307);     // OFDM.c:945
     if (L < 400 || L > OFDM_CAPTURE_MAX_LEN)

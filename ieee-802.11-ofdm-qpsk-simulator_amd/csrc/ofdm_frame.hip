@@ -2175,6 +2175,24 @@ int ofdm_receiver(ofdm_ctx *ctx, const float *capture, const ofdm_rx_opts *opts,
     HIPOK(hipMemcpyAsync(words, base + off_bits, sizeof(words), hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipMemcpyAsync(eq, base + off_eq, sizeof(eq), hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
+    if (ints[2]) {
+        // The capture ends before its packet does.  A data symbol wholly past the end reaches the demapper as exact
+        // zeros, where the kernel's error counts go by the sign bit of u = +-0 (ofdm_rxcommon.h demap_sub), an accident
+        // of S, while the bits and subcarriers above follow the reference's "Z > 0" (zero and NaN decide "-",
+        // OFDM.c:858-866).  The BER and the post-slicer EVM are recounted here from those by that rule; for every
+        // other value the two rules agree.
+        uint32_t berr = 0u, ax = 0u;
+        for (int k = 0; k < 3 * nd; ++k) berr += (uint32_t)__builtin_popcount(words[k] ^ xa.table[k]);
+        for (int j = 0; j < 48 * nd; ++j) {
+            const int d = j / 48, m = j % 48;
+            const uint32_t *w = xa.table + 3 * d;
+            const uint32_t b0 = (w[(2 * m) >> 5] >> (31 - ((2 * m) & 31))) & 1u;
+            const uint32_t b1 = (w[(2 * m + 1) >> 5] >> (31 - ((2 * m + 1) & 31))) & 1u;
+            ax += (uint32_t)((eq[j].x > 0.f) != (b0 == b1)) + (uint32_t)((eq[j].y > 0.f) != (b0 == 0u));   // D10
+        }
+        res[2] = (float)berr / (96.0f * (float)nd);
+        res[1] = ax ? (float)(10.0 * std::log10(2.0 * (double)ax / (48.0 * nd))) : -INFINITY;
+    }
     if (res3) { res3[0] = res[0]; res3[1] = res[1]; res3[2] = res[2]; }
     if (ints4) { ints4[0] = ints[0]; ints4[1] = ints[1]; ints4[2] = ints[2]; ints4[3] = nd; }
     if (bits_out)

@@ -295,7 +295,23 @@ struct DecArgs {
     int32_t wave_floats;     // floats per wave: two planes and fr[]
     float taps[21];
     uint32_t dtable[4 * SDEC_MAX_DATA];
+    uint32_t ztable[SDEC_MAX_DATA];   // per data symbol, were it all zeros: bit errors | slicer axis errors << 16 (stream_zero_errors)
 };
+
+// The errors of a data symbol that arrives as 64 exact zeros (its window lies wholly past the stream's end), as
+// ofdm_captures.hip counts them: the reference's slicer decides "-" on both axes for a zero (OFDM.c:858-866), the
+// demapper (1, 0) for every pair, so the counts depend on the payload alone.  w: the symbol's 96 payload bits, MSB
+// first; an axis is wrong where the truth is "+": re > 0 iff b0 == b1, im > 0 iff b0 == 0 (D10).
+static uint32_t stream_zero_errors(const uint32_t w[3]) {
+    uint32_t be = 0u, ax = 0u;
+    for (int k = 0; k < 3; ++k) be += (uint32_t)__builtin_popcount(w[k] ^ 0xAAAAAAAAu);
+    for (int m = 0; m < 48; ++m) {
+        const uint32_t b0 = (w[(2 * m) >> 5] >> (31 - ((2 * m) & 31))) & 1u;
+        const uint32_t b1 = (w[(2 * m + 1) >> 5] >> (31 - ((2 * m + 1) & 31))) & 1u;
+        ax += (uint32_t)(b0 == b1) + (uint32_t)(b0 == 0u);
+    }
+    return be | (ax << 16);
+}
 
 // LDS ordering between the lanes of one wave (the block's other waves run other packets)
 __device__ __forceinline__ void sdec_wave_sync() {
@@ -379,6 +395,8 @@ __global__ __launch_bounds__(64 * SDEC_MAX_WAVES) void stream_decode_kernel(DecA
         sdec_wave_sync();
         // ---- RRC matched filter at the down-sampled instants: stream sample p + 2 ii - tt is plane index 20 + 2 ii - tt ----
         const bool oob = p + 2 * (int64_t)(nfr - 1) >= a.n + 20;       // the reference reads past its buffer
+        // the first data symbol wholly past the end: the least d >= 0 with p + 2 (336 + 80 d) >= n + 20; D when none
+        const int zfirst = (int)std::min<int64_t>(std::max<int64_t>((a.n - 652 - p + 159) / 160, 0), nd);
         for (int ii = lane; ii < nfr; ii += 64) {
             if (!sdec_needed(ii)) continue;
             const int n = 20 + 2 * ii;
@@ -494,6 +512,11 @@ __global__ __launch_bounds__(64 * SDEC_MAX_WAVES) void stream_decode_kernel(DecA
             }
         }
         // ---- the packet's totals in symbol order, its record and its counter terms ----
+        // A data symbol whose window lies wholly past the stream's end reached the demapper as 64 exact zeros, where the
+        // sign bit of u = +-0 that demap_sub counts is an accident of S; the reference decides "-" on both axes for a zero,
+        // as the output pass above does, so that symbol's counts are the payload's own (ztable; capture_rx_kernel's rule:
+        // symbols zfirst .. D - 1, a wave-uniform, rare branch after the transforms).  Its EVM term needs nothing: u' =
+        // +-0 gives |0 - d|^2 either way.
         const float fev = dlane ? finish_evm<2>(st) : 0.f;
         const uint32_t bev = dlane ? st.be : 0u, axv = dlane ? st.ax : 0u;
         float fe = 0.f;
@@ -504,9 +527,19 @@ __global__ __launch_bounds__(64 * SDEC_MAX_WAVES) void stream_decode_kernel(DecA
             ferr += (uint32_t)__shfl((int)bev, src, 64);
             fax += (uint32_t)__shfl((int)axv, src, 64);
         }
+        if (zfirst < nd) {
+            for (int d = zfirst; d < nd; ++d) {
+                const int src = 4 * (d / 3) + 1 + d % 3;
+                const uint32_t z = a.ztable[d];
+                ferr += (z & 0xffffu) - (uint32_t)__shfl((int)bev, src, 64);
+                fax += (z >> 16) - (uint32_t)__shfl((int)axv, src, 64);
+            }
+        }
         if (lane == 0) {
             const float N = 48.0f * (float)nd;
-            const float db = fe > 0.f ? fmaxf(3.01029995663981195214f * __builtin_amdgcn_logf(fe / N), -400.f) : -400.f;
+            // a NaN sum (the stream ends before the long training symbols: S = 0, Z = 0 / 0) stays NaN, as the reference's
+            const float db = fe > 0.f ? fmaxf(3.01029995663981195214f * __builtin_amdgcn_logf(fe / N), -400.f)
+                                      : (fe == fe ? -400.f : fe);
             const float dbp = fax > 0u ? 3.01029995663981195214f * __builtin_amdgcn_logf(2.0f * (float)fax / N) : -INFINITY;
             ofdm_capture_result *r = &pkt->r;
             r->bit_err = (int32_t)ferr;
@@ -524,8 +557,10 @@ __global__ __launch_bounds__(64 * SDEC_MAX_WAVES) void stream_decode_kernel(DecA
                 atomicAdd(&acc[OFDM_C_BIT_ERR], (unsigned long long)ferr);
                 atomicAdd(&acc[OFDM_C_FRAME_ERR], (unsigned long long)(ferr > 0u));
                 atomicAdd(&acc[OFDM_C_EVM_POST_AXIS], (unsigned long long)fax);
-                atomicAdd(&acc[OFDM_C_EVM_PRE_Q], (unsigned long long)__float2ll_rn(fe * Q));
-                atomicAdd(&acc[OFDM_C_EVMDB_PRE_Q], (unsigned long long)__float2ll_rn(db * Q));
+                if (fabsf(fe) < INFINITY) {                          // a non-finite term is left out, never converted
+                    atomicAdd(&acc[OFDM_C_EVM_PRE_Q], (unsigned long long)__float2ll_rn(fe * Q));
+                    atomicAdd(&acc[OFDM_C_EVMDB_PRE_Q], (unsigned long long)__float2ll_rn(db * Q));
+                }
                 if (fax > 0u) {
                     atomicAdd(&acc[OFDM_C_EVMDB_POST_Q], (unsigned long long)__float2ll_rn(dbp * Q));
                     atomicAdd(&acc[OFDM_C_EVMDB_POST_FINITE], 1ull);
@@ -587,7 +622,10 @@ extern "C" int ofdm_receive_stream(ofdm_ctx *ctx, const void *d_samples, int64_t
     DecArgs da{};
     uint32_t table[3 * LONG_MAX_FRAMES];
     da.n_data = payload_table_long(payload, c->message, table);
-    for (int d = 0; d < da.n_data; ++d) demap_words(table + 3 * d, da.dtable + 4 * d);
+    for (int d = 0; d < da.n_data; ++d) {
+        demap_words(table + 3 * d, da.dtable + 4 * d);
+        da.ztable[d] = stream_zero_errors(table + 3 * d);
+    }
     const int nfr = 320 + 80 * da.n_data;
     // the decode block's LDS, checked before anything is launched
     da.plane = (2 * nfr + 19 + 3) & ~3;

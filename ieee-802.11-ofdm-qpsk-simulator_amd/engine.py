@@ -373,10 +373,11 @@ class Engine:
                                                             trial, snr_index), "transmission_over_air")
         return out
 
-    def receiver(self, capture: np.ndarray, mode: str = "c", payload: str = "message"):
+    def receiver(self, capture: np.ndarray, mode: str = "c", payload: str = "message", opts: dict | None = None):
         """Receiver() on one capture (OFDM.c:941-1182): metrics, packet_idx, bits, equalised
-        subcarriers and the decoded text (Message_Generator, OFDM.c:921-939)."""
-        opts = make_rx_opts(mode)
+        subcarriers and the decoded text (Message_Generator, OFDM.c:921-939).  opts: single fields of ofdm_rx_opts
+        over the mode's (abi.make_rx_opts), e.g. {"cap_len": 1100} for a capture shorter than its packet."""
+        opts = make_rx_opts(mode, opts=opts)
         nd = self.payload_frames(payload)
         L = opts.cap_len or abi.capture_len(nd)
         cap = np.ascontiguousarray(capture[:L], np.complex64)
@@ -392,9 +393,10 @@ class Engine:
                     bits=bits, eq=eq.view(np.complex64).copy(), message=decode_message(bits))
 
     def receive_captures(self, captures, mode: str = "c", payload: str = "message", want_bits: bool = True,
-                         want_eq: bool = False, counters=None) -> dict:
+                         want_eq: bool = False, counters=None, opts: dict | None = None) -> dict:
         """Receiver() over a batch of caller-supplied captures (ofdm_receive_captures, include/ofdm_mi355x_captures.h):
-        one record per capture, the two CFO estimates included.
+        one record per capture, the two CFO estimates included.  opts: single fields of ofdm_rx_opts over the mode's
+        (abi.make_rx_opts), e.g. {"cap_len": 1100} for captures shorter than their packet.
 
         captures: a torch complex64 tensor [n, L >= cap_len] on this engine's device, used in place (its row stride
         is the pitch; it is never written), or a numpy complex64 array of that shape, uploaded once.  Anything else
@@ -404,7 +406,7 @@ class Engine:
         messages None when not asked for.  Outputs are allocated by torch on the current stream; only `messages`
         (want_bits) and numpy results wait for the device."""
         torch = _torch()
-        opts = make_rx_opts(mode)
+        opts = make_rx_opts(mode, opts=opts)
         nd = self.payload_frames(payload)
         L = opts.cap_len or abi.capture_len(nd)
         dev = torch.device("cuda", self.device)
@@ -462,9 +464,11 @@ class Engine:
 
     def receive_stream(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
                        want_bits: bool = True, want_eq: bool = False, want_metric: bool = False,
-                       want_cross: bool = False, counters=None, keep_device: bool = False) -> dict:
+                       want_cross: bool = False, counters=None, keep_device: bool = False,
+                       opts: dict | None = None) -> dict:
         """Every packet of one recording of any length (ofdm_receive_stream, include/ofdm_mi355x_stream.h): the
         reference's detection rule once over the whole recording, then the receiver chain on every packet found.
+        opts: single fields of ofdm_rx_opts over the mode's (abi.make_rx_opts; a stream has no cap_len to set).
 
         samples: a one-dimensional contiguous torch complex64 tensor on this engine's device, used in place (never
         written), or a numpy complex64 array, uploaded once.  Anything else raises ValueError before any launch.
@@ -477,7 +481,7 @@ class Engine:
         waits for the device.  keep_device: also return d_packets (uint8 [rows, 64]), d_count (int64 [2]) and d_words
         (int32 [rows, 3 D], None without want_bits), the device tensors the kernels wrote, for score_packets."""
         torch = _torch()
-        opts = make_rx_opts(mode)
+        opts = make_rx_opts(mode, opts=opts)
         nd = self.payload_frames(payload)
         dev = torch.device("cuda", self.device)
         from_numpy = isinstance(samples, np.ndarray)

@@ -84,8 +84,12 @@ typedef struct {
     int32_t cap_len;        /* capture length: 0 = int(0.307 x waveform length) (OFDM.c:945; 3008 for the
                                reference message) or e.g. 3000 (Tester.m:151) */
     int32_t float_cfo;      /* 1: CFO estimates rounded to float as OFDM.c:798,821 */
-    int32_t matlab_slicer;  /* 1: MATLAB zero handling in slicer/demod (Tester.m:338-411) */
-    int32_t float_taps;     /* 1: fp32 RRC taps (OFDM.c:32) -- 0: double rcosdesign taps */
+    int32_t matlab_slicer;  /* 1: MATLAB zero handling in slicer/demod (Tester.m:338-411).  Accepted; the GPU receivers
+                               apply the C rule whatever it says: a zero or NaN component decides "-" (Z > 0 fails,
+                               OFDM.c:858-866).  The MATLAB rule differs only for an exactly zero component, which
+                               the Tester's known answer never produces */
+    int32_t float_taps;     /* 1: fp32 RRC taps (OFDM.c:32) -- 0: double rcosdesign taps.  Accepted; the GPU receivers
+                               filter with the fp32 taps whatever it says */
     int32_t fixed_start;    /* >=0: capture offset for every trial (Tester.m:152); -1: Philox draw (OFDM.c:949) */
     int32_t word_stats;     /* 1: word-length analysis per trial into OFDM_C_WL_* (frame sweeps) */
     int32_t reserved[2];
@@ -192,7 +196,10 @@ int ofdm_transmission_over_air(ofdm_ctx *ctx, const float *tx, float *ota, int32
 /* "Receiver" (OFDM.c:941-1165) on one host capture already offset (cap_len samples; cap_len 0 =
  * int(0.307 x waveform length), OFDM.c:945): returns res3 = {EVM_dB, EVM_AGC_dB, BER},
  * ints4 = {packet_idx, sync_fail, oob, D}, and optionally the demodulated bits (int32 [D*96]) and
- * equalised subcarriers (float2 [D*48]), D = ofdm_payload_frames(payload). */
+ * equalised subcarriers (float2 [D*48]), D = ofdm_payload_frames(payload).  A capture that ends before its
+ * packet does (oob) reads zeros past its end; the BER and EVM_AGC_dB of such a capture are counted from the
+ * returned bits and subcarriers by the reference's rule (a data symbol wholly past the end: subcarriers 0,
+ * bits (1, 0)), as the batched receiver of ofdm_mi355x_captures.h counts them. */
 int ofdm_receiver(ofdm_ctx *ctx, const float *capture, const ofdm_rx_opts *opts, int payload,
                   float *res3, int32_t *ints4, int32_t *bits_out, float *eq_out);
 /* "Word_Optimization_Analysis(Rx_filter_signal, len)" (OFDM.c:38-73, called at :967): the RRC
@@ -201,7 +208,10 @@ int ofdm_receiver(ofdm_ctx *ctx, const float *capture, const ofdm_rx_opts *opts,
 int ofdm_word_length_report(ofdm_ctx *ctx, const float *capture, int32_t cap_len, float *out3, int32_t *bits);
 /* Batched frame-mode sweep: n_trials reference trials per SNR point (capture offset + noise from
  * Philox); host counters [n_snr][OFDM_NCOUNTERS]; optional per-trial packet_idx
- * [n_snr][n_trials]. */
+ * [n_snr][n_trials].  With a cap_len too short for the packet, the bit and axis errors of a data symbol that
+ * lies wholly past the capture's end are unspecified here (the sweep's symbol kernel counts the sign bit of an
+ * exactly zero value); OFDM_C_OOB counts those trials, and the batched receiver of ofdm_mi355x_captures.h
+ * decodes such captures by the reference's rule. */
 int ofdm_frame_sweep(ofdm_ctx *ctx, const ofdm_cfg *cfg, const ofdm_rx_opts *opts,
                      const double *snr_db, int n_snr, uint64_t first_trial, int64_t n_trials,
                      int64_t *counters, int32_t *packet_idx);

@@ -26,7 +26,18 @@
  *              receiver uses, coarse and fine CFO (float_cfo), one combined rotation, 64-point FFTs, LS
  *              estimate, ZF equaliser, slicer, demap, EVM and BER against the context's payload.
  *   bounds     samples outside [0, n) read as zero; OFDM_CAPTURE_OOB is set when
- *              p + 2 (nfr - 1) >= n + 20, nfr = 320 + 80 D.
+ *              p + 2 (nfr - 1) >= n + 20, nfr = 320 + 80 D: the recording's last packet, cut off, comes back
+ *              with flags 2 | 4.  Its record follows ofdm_receive_captures' rule with n for cap_len: a data
+ *              symbol wholly past the end (p + 2 (336 + 80 d) - 20 >= n) has subcarriers 0 and bits (1, 0),
+ *              and the error counts say the same; a stream that ends before the long training symbols
+ *              (p + 364 >= n; the front is still confirmed when n > front + 277) has S = 0 in every bin, NaN
+ *              subcarriers, bits (1, 0) throughout, NaN evm_pre_sum and evm_db_pre and a finite evm_db_post,
+ *              which is Receiver()'s own answer (tests/test_gpu_oob.py).
+ *   input      samples must be finite: the metric slides its sums in fp32, so one NaN or infinity stays in a
+ *              lane's sums for the rest of its run, where Receiver() recomputes every window.  0.75 p^2 and
+ *              |c|^2 are fp32, p the sum of 32 |sample|^2: p^2 must stay inside the fp32 range, sample
+ *              magnitudes between about 1e-8 and 1e8.  A recording scaled by 2^-12 or 2^12 from
+ *              Transmitter()'s own level decodes bit for bit as the unscaled one.
  * Fronts are at least 301 positions apart, so a stream holds at most n / 301 + 1 of them: one slot per 301
  * positions holds at most one front (the bound to size max_packets with).
  *
@@ -61,7 +72,8 @@ typedef struct {                 /* 64 bytes, one per packet */
 } ofdm_stream_packet;
 
 /* Detects and decodes every packet of the n_samples interleaved fp32 complex samples at d_samples (device,
- * 8-byte aligned, only read).  opts->float_cfo means what it means in ofdm_receive_captures; cap_len and
+ * 8-byte aligned, only read).  opts->float_cfo means what it means in ofdm_receive_captures; matlab_slicer
+ * and float_taps change nothing, as there (fp32 taps, the C slicer: zero and NaN decide "-"); cap_len and
  * fixed_start are ignored; word_stats != 0 is OFDM_E_ARG.  payload is MESSAGE or TESTER and fixes the data
  * symbols per packet, D = ofdm_payload_frames(payload).
  *   d_packets   ofdm_stream_packet[max_packets]          (device, required) ascending packet_pos
@@ -70,7 +82,8 @@ typedef struct {                 /* 64 bytes, one per packet */
  *   d_bits      uint32 [max_packets][3 D], MSB-first     (device, optional)
  *   d_eq        float2 [max_packets][48 D]               (device, optional)
  *   d_counters  int64 [OFDM_NCOUNTERS], one row          (device, optional, ADDED to: exactly the reduction
- *               of the written records by the rule of ofdm_receive_captures)
+ *               of the written records by the rule of ofdm_receive_captures; a non-finite evm_pre_sum is
+ *               left out of EVM_PRE_Q and EVMDB_PRE_Q, as a -inf evm_db_post is out of EVMDB_POST_Q)
  *   d_metric    float  [n_samples - 47], M[i]            (device, optional; NaN where the power is zero)
  *   d_cross     uint32 [ceil((n_samples - 47) / 32)], crossing i is bit i & 31 of word i >> 5
  *                                                        (device, optional)

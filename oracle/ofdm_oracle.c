@@ -299,10 +299,7 @@ void orc_receiver_frame(const double *capture, const orc_rx_opts *o, const int *
                         double *Yf, double *nopilot, int *bits_out, orc_rx_info *info)
 {
     const cplx *r = (const cplx *)capture;
-    const int L = o->cap_len, LF = L + 20;
-    const int fsz = 320 + 80 * nf;
-    double h[21];
-    orc_rrc_taps(o->float_taps, h);
+    const int L = o->cap_len;
 
     /* Packet_Detection on the UNFILTERED capture, no conjugate (OFDM.c:659-683) */
     int lc = L - 16 + 1 - 32;
@@ -320,6 +317,22 @@ void orc_receiver_frame(const double *capture, const orc_rx_opts *o, const int *
     if (corr) memcpy(corr, M, sizeof(double) * lc);
     int pidx = packet_selection(M, lc);
     free(M);
+    orc_decode_at(capture, o, truth_bits, nf, pidx, rxframe, coarse, fine, Hout, Yf, nopilot, bits_out, info);
+}
+
+/* Receiver() from the matched filter on (OFDM.c:962-1165) at a given packet_idx: what orc_receiver_frame runs after
+   its own Packet_Selection.  Callers that place the packet themselves (the stream rule on a recording's cut-off last
+   packet, whose window holds no second front) decode here.  info->sync_fail is packet_idx == 0, as Receiver()'s. */
+void orc_decode_at(const double *capture, const orc_rx_opts *o, const int *truth_bits, int nf, int pidx,
+                   double *rxframe, double *coarse, double *fine, double *Hout,
+                   double *Yf, double *nopilot, int *bits_out, orc_rx_info *info)
+{
+    const cplx *r = (const cplx *)capture;
+    const int L = o->cap_len, LF = L + 20;
+    const int fsz = 320 + 80 * nf;
+    const int lc = L - 16 + 1 - 32;
+    double h[21];
+    orc_rrc_taps(o->float_taps, h);
 
     /* matched filter (Convolution, OFDM.c:965) evaluated at the down-sampled taps (OFDM.c:992) */
     cplx *fr = calloc(fsz, sizeof(cplx));

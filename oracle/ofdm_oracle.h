@@ -91,6 +91,10 @@ typedef struct {
 void orc_receiver_frame(const double *capture, const orc_rx_opts *o, const int *truth_bits, int nf,
                         double *corr, double *rxframe, double *coarse, double *fine, double *H,
                         double *Yf, double *nopilot, int *bits_out, orc_rx_info *info);
+/* the same from the matched filter on, at a given packet_idx (orc_receiver_frame calls it with its own selection) */
+void orc_decode_at(const double *capture, const orc_rx_opts *o, const int *truth_bits, int nf, int packet_idx,
+                   double *rxframe, double *coarse, double *fine, double *H,
+                   double *Yf, double *nopilot, int *bits_out, orc_rx_info *info);
 
 /* ---- Monte-Carlo twins of the HIP sweeps (small sizes only) ---- */
 void orc_symbol_sweep(const orc_cfg *cfg, const double *snr_db, int n_snr,

@@ -101,6 +101,8 @@ class Oracle:
         L.orc_time_symbol_sweep.restype = C.c_double
         L.orc_receiver_frame.argtypes = [C.c_void_p, C.POINTER(_RxOpts), C.c_void_p, C.c_int] + \
             [C.c_void_p] * 8 + [C.POINTER(_RxInfo)]
+        L.orc_decode_at.argtypes = [C.c_void_p, C.POINTER(_RxOpts), C.c_void_p, C.c_int, C.c_int] + \
+            [C.c_void_p] * 7 + [C.POINTER(_RxInfo)]
         L.orc_frame_waveform.restype = C.c_int
         L.orc_message_bits.restype = C.c_int
         L.orc_set_message.restype = C.c_int
@@ -204,29 +206,54 @@ class Oracle:
         self.lib.orc_frame_waveform(_p(b), nf, CONV[conv], int(float_taps), reps, _p(o))
         return i2c(o)
 
-    def receiver_frame(self, capture: np.ndarray, truth_bits, mode="c", dumps=False):
+    def receiver_frame(self, capture: np.ndarray, truth_bits, mode="c", dumps=False, cap_len=None, opts=None,
+                       packet_idx=None):
+        """orc_receiver_frame on capture[:cap_len].  cap_len: the capture's length when it is not the mode's own (a
+        capture shorter than its packet: samples past its end read as zero and set oob).  opts: a dict of single
+        fields of orc_rx_opts (float_cfo, matlab_slicer, float_taps) set over the mode's.  packet_idx: decode there
+        instead of running Packet_Selection (orc_decode_at; no corr dump)."""
         tb = np.ascontiguousarray(truth_bits, np.int32)
         nf = len(tb) // 96
-        opts = self.rx_opts(mode, nf)
-        cap = c2i(capture[:opts.cap_len])
+        o = self.rx_opts(mode, nf)
+        if cap_len is not None:
+            o.cap_len = int(cap_len)
+        for k, v in (opts or {}).items():
+            if k not in ("float_cfo", "matlab_slicer", "float_taps"):
+                raise ValueError(f"unknown receiver option {k!r}")
+            setattr(o, k, int(v))
+        if len(capture) < o.cap_len or o.cap_len < 48:
+            raise ValueError(f"capture holds {len(capture)} samples, cap_len is {o.cap_len}")
+        cap = c2i(capture[:o.cap_len])
         fsz = 320 + 80 * nf
         info = _RxInfo()
         bits = np.zeros(96 * nf, np.int32)
         d = None
+        keys = ("corr", "rxframe", "coarse", "fine", "H", "Yf", "nopilot")
         if dumps:
-            lc = opts.cap_len - 47
+            lc = o.cap_len - 47
             d = dict(corr=np.zeros(lc), rxframe=np.zeros(2 * fsz), coarse=np.zeros(2 * fsz),
                      fine=np.zeros(2 * fsz), H=np.zeros(128), Yf=np.zeros(128 * nf),
                      nopilot=np.zeros(96 * nf))
-            ptrs = [_p(d[k]) for k in ("corr", "rxframe", "coarse", "fine", "H", "Yf", "nopilot")]
+            if packet_idx is not None:
+                del d["corr"]
+            ptrs = [_p(d[k]) for k in keys if k in d]
         else:
-            ptrs = [None] * 7
-        self.lib.orc_receiver_frame(_p(cap), C.byref(opts), _p(tb), nf, *ptrs, _p(bits), C.byref(info))
+            ptrs = [None] * (7 if packet_idx is None else 6)
+        if packet_idx is None:
+            self.lib.orc_receiver_frame(_p(cap), C.byref(o), _p(tb), nf, *ptrs, _p(bits), C.byref(info))
+        else:
+            self.lib.orc_decode_at(_p(cap), C.byref(o), _p(tb), nf, int(packet_idx), *ptrs, _p(bits), C.byref(info))
         out = dict(bits=bits, packet_idx=info.packet_idx, sync_fail=info.sync_fail, oob=info.oob,
                    res=np.array(info.res[:]), cfo=np.array(info.cfo[:]))
         if d is not None:
             out.update({k: (v if k == "corr" else i2c(v)) for k, v in d.items()})
         return out
+
+    def decode_at(self, capture: np.ndarray, truth_bits, packet_idx: int, mode="c", dumps=False, cap_len=None,
+                  opts=None):
+        """Receiver() from the matched filter on at a given packet_idx (orc_decode_at): receiver_frame without its
+        Packet_Selection."""
+        return self.receiver_frame(capture, truth_bits, mode, dumps, cap_len, opts, packet_idx=int(packet_idx))
 
     def symbol_sweep(self, cfg: _Cfg, snr_db, first_frame=0, n_frames=64, dumps=False):
         snr = np.ascontiguousarray(snr_db, np.float64)

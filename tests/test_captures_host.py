@@ -96,6 +96,24 @@ def test_reduce_capture_records_rule(pkg):
     assert c[abi.C_OOB] == 1 and not c[abi.C_WL_MIN_Q:].any()
 
 
+def test_reduce_capture_records_leaves_non_finite_terms_out(pkg):
+    """A capture that ends before its long training symbols has S = 0 and Z = 0 / 0: evm_pre_sum and evm_db_pre are
+    NaN, and both are left out of the row, as a -inf evm_db_post is; everything else of the record counts."""
+    abi = pkg.abi
+    rec = np.zeros(3, abi.capture_result_dtype())
+    rec["flags"] = [0, 2, 2]
+    rec["bit_err"] = [0, 100, 96]
+    rec["post_axis_err"] = [0, 101, 90]
+    rec["evm_pre_sum"] = np.float32([0.125, np.nan, np.inf])
+    rec["evm_db_pre"] = np.float32([-28.5, np.nan, np.inf])
+    rec["evm_db_post"] = np.float32([-np.inf, 0.25, -0.25])
+    c = abi.reduce_capture_records(rec, 2)
+    assert list(c[:3]) == [3, 6, 576] and c[abi.C_EVM_TERMS] == 288
+    assert c[abi.C_BIT_ERR] == 196 and c[abi.C_EVM_POST_AXIS] == 191
+    assert c[abi.C_EVM_PRE_Q] == 0.125 * 2 ** 20 and c[abi.C_EVMDB_PRE_Q] == -28.5 * 2 ** 20
+    assert c[abi.C_EVMDB_POST_Q] == 0 and c[abi.C_EVMDB_POST_FINITE] == 2 and c[abi.C_OOB] == 2
+
+
 # ---------------------------------------------------------------- channel.make_captures on the CPU
 @pytest.fixture(scope="module")
 def wave(oracle):
