@@ -35,6 +35,7 @@ K_STREAM_DETECT, K_STREAM_SELECT, K_STREAM_DECODE = 4, 5, 6     # OFDM_K_STREAM_
 K_TRANSMIT = 7                                                   # OFDM_K_TRANSMIT (ofdm_mi355x_tx.h)
 K_CHANNEL, K_SCORE = 8, 9                                        # OFDM_K_CHANNEL, OFDM_K_SCORE (ofdm_mi355x_channel.h)
 K_FADE, K_DRAW_TAPS = 10, 11                                     # OFDM_K_FADE, OFDM_K_DRAW_TAPS (ofdm_mi355x_fading.h)
+K_STREAM_DETECT_CONJ = 12                                        # OFDM_K_STREAM_DETECT_CONJ (ofdm_mi355x_detect.h)
 
 # every entry point of the header, with ctypes argument types
 _V = C.c_void_p
@@ -139,6 +140,18 @@ _FADING_SIGS = {
 FADING_EXPORTS = tuple(_FADING_SIGS)
 FADE_MAX_TAPS = 32                 # OFDM_FADE_MAX_TAPS
 
+# the extension header include/ofdm_mi355x_detect.h (an optional detector and a threshold for the stream receiver); the
+# export lists above and ABI_VERSION do not change with it
+DETECT_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_detect.h"
+_DETECT_SIGS = {
+    "ofdm_stream_positions": (C.c_int64, [C.c_int64, C.c_int]),
+    "ofdm_receive_stream_ex": (C.c_int, [_V, _V, C.c_int64, _V, _V, C.c_int, C.c_int64, _V, _V, _V, _V, _V, _V, _V]),
+}
+DETECT_EXPORTS = tuple(_DETECT_SIGS)
+DETECTOR = {"reference": 0, "conjugate": 1}      # OFDM_DETECT_REFERENCE, OFDM_DETECT_CONJUGATE
+DETECT_THRESHOLD = 0.75                          # OFDM_DETECT_THRESHOLD
+DETECT_HALO = {"reference": 47, "conjugate": 63}  # Lc = n - halo
+
 
 class OfdmError(RuntimeError):
     pass
@@ -194,6 +207,32 @@ def capture_result_dtype():
     return np.dtype([("packet_idx", "<i4"), ("flags", "<i4"), ("bit_err", "<i4"), ("post_axis_err", "<i4"),
                      ("evm_pre_sum", "<f4"), ("evm_db_pre", "<f4"), ("evm_db_post", "<f4"), ("ber", "<f4"),
                      ("cfo_coarse_hz", "<f4"), ("cfo_fine_hz", "<f4"), ("reserved", "<i4", (2,))])
+
+
+class StreamOpts(C.Structure):
+    """ofdm_stream_opts (32 bytes)"""
+    _fields_ = [("detector", C.c_int32), ("threshold", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
+def make_stream_opts(detector: str = "reference", threshold: float = DETECT_THRESHOLD) -> StreamOpts:
+    """ofdm_stream_opts for Engine.receive_stream: ValueError for an unknown detector or a threshold that is NaN or
+    outside (0, 1) -- what ofdm_receive_stream_ex refuses, refused before the call."""
+    if detector not in DETECTOR:
+        raise ValueError(f"detector must be one of {tuple(DETECTOR)}, got {detector!r}")
+    try:
+        thr = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"threshold must be a number inside (0, 1), got {threshold!r}") from None
+    if not 0.0 < C.c_float(thr).value < 1.0:
+        raise ValueError(f"threshold must be inside (0, 1), got {threshold!r}")
+    return StreamOpts(DETECTOR[detector], thr)
+
+
+def stream_positions(n: int, detector: str = "reference") -> int:
+    """Lc of ofdm_stream_positions: n - 47 (reference) or n - 63 (conjugate), 0 when there are no positions"""
+    if detector not in DETECTOR:
+        raise ValueError(f"detector must be one of {tuple(DETECTOR)}, got {detector!r}")
+    return max(int(n) - DETECT_HALO[detector], 0)
 
 
 class StreamPacket(C.Structure):
@@ -305,7 +344,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
     for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS,
-                              **_CHANNEL_SIGS, **_FADING_SIGS}.items():
+                              **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

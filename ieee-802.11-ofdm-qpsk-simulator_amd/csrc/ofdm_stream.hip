@@ -21,12 +21,15 @@
 //     packet_pos, with the LAST_FRONT flag.  No arrival-order append anywhere: the output is deterministic.
 //   stream_decode_kernel<OUT> : one wave per packet, W waves per block, looping over d_count.  A wave stages only
 //     [p - 20, p + 2 nfr - 2] (2 nfr + 19 samples, zero outside the stream) and runs capture_rx_kernel's chain on it.
+// ofdm_receive_stream_ex (ofdm_stream_conj.hip) enters through stream_receive with a detector of its own
+// (ofdm_stream_detect.h): another detection launch, then the selection and decode launches of this file.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include "ofdm_mi355x_stream.h"
 #include "ofdm_ctx.h"
 #include "ofdm_rxcommon.h"
+#include "ofdm_stream_detect.h"
 
 namespace ofdm {
 
@@ -59,14 +62,7 @@ constexpr uint64_t sdec_ltf_neg() {
 constexpr uint64_t SDEC_LTF_NEG = sdec_ltf_neg();
 static_assert(sizeof(ofdm_stream_packet) == 64, "ofdm_stream_packet is 64 bytes");
 
-struct DetArgs {
-    const float2 *x;
-    int64_t n, lc, tiles, words;   // samples, positions, tiles, bitmap words
-    uint32_t *bitmap;              // scratch, padded to whole 16-byte groups
-    uint32_t *cross;               // the caller's copy (optional)
-    float *metric;                 // optional
-};
-
+// DetArgs: ofdm_stream_detect.h (shared with the detectors of ofdm_stream_conj.hip)
 template <bool METRIC>
 __global__ __launch_bounds__(SD_THREADS) void stream_detect_kernel(DetArgs a) {
     __shared__ __attribute__((aligned(16))) float re[SD_PLANE];
@@ -594,14 +590,12 @@ static void stream_taps(float out[21]) {
     for (int i = 0; i < 10; ++i) out[20 - i] = out[i];
 }
 
-}  // namespace ofdm
-
-using namespace ofdm;
-
-extern "C" int ofdm_receive_stream(ofdm_ctx *ctx, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
-                                   int payload, int64_t max_packets, void *d_packets, void *d_count, void *d_bits,
-                                   void *d_eq, void *d_counters, void *d_metric, void *d_cross) {
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+// ofdm_receive_stream's body.  det (ofdm_stream_detect.h): another detection launch in place of stream_detect_kernel,
+// with its own halo; everything after the bitmap -- selection, compaction, decode -- is the same launches either way.
+int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts, int payload,
+                   int64_t max_packets, void *d_packets, void *d_count, void *d_bits, void *d_eq, void *d_counters,
+                   void *d_metric, void *d_cross, const StreamDetector *det) {
+    const int halo = det ? det->halo : 47;
     if (!c) return set_error(OFDM_E_ARG, "ctx is NULL");
     if (!opts) return set_error(OFDM_E_ARG, "opts is NULL");
     if (n_samples < 0) return set_error(OFDM_E_ARG, "n_samples %lld is negative", (long long)n_samples);
@@ -614,7 +608,7 @@ extern "C" int ofdm_receive_stream(ofdm_ctx *ctx, const void *d_samples, int64_t
     if (!d_packets && max_packets > 0) return set_error(OFDM_E_ARG, "d_packets is required");
     if (reinterpret_cast<uintptr_t>(d_samples) & 7u) return set_error(OFDM_E_ARG, "d_samples must be 8-byte aligned");
     if (hipSetDevice(c->device) != hipSuccess) return set_error(OFDM_E_HIP, "hipSetDevice(%d) failed", c->device);
-    if (n_samples < 48) {                                            // no positions, no packets
+    if (n_samples <= halo) {                                         // no positions, no packets
         if (hipMemsetAsync(d_count, 0, 2 * sizeof(int64_t), c->stream) != hipSuccess)
             return set_error(OFDM_E_HIP, "hipMemsetAsync(d_count) failed");
         return OFDM_OK;
@@ -645,7 +639,7 @@ extern "C" int ofdm_receive_stream(ofdm_ctx *ctx, const void *d_samples, int64_t
     if (lds > limit) return set_error(OFDM_E_ARG, "dynamic LDS request %zu above the limit %zu", lds, limit);
 
     // scratch: the crossing bitmap (whole 16-byte groups), the front slots, the selection blocks' counts and maxima
-    const int64_t lc = n_samples - 47;
+    const int64_t lc = n_samples - halo;
     const int64_t words = (lc + 31) / 32, tiles = (lc + SD_TILE - 1) / SD_TILE;
     const int64_t nslots = (lc + SS_SLOT - 1) / SS_SLOT, nblocks = (nslots + SS_THREADS - 1) / SS_THREADS;
     if (tiles > 0x7fffffffll || nblocks > 0x7fffffffll)
@@ -679,12 +673,14 @@ extern "C" int ofdm_receive_stream(ofdm_ctx *ctx, const void *d_samples, int64_t
 
     // one tile per block up to a grid the loop in the kernel wraps (the results do not depend on it)
     const dim3 dgrid((unsigned)std::min<int64_t>(tiles, 1 << 20));
-    c->tic(OFDM_K_STREAM_DETECT);
-    if (ta.metric) hipLaunchKernelGGL(stream_detect_kernel<true>, dgrid, dim3(SD_THREADS), 0, c->stream, ta);
+    c->tic(det ? det->kernel : OFDM_K_STREAM_DETECT);
+    if (det) det->launch(det, dgrid, c->stream, ta);
+    else if (ta.metric) hipLaunchKernelGGL(stream_detect_kernel<true>, dgrid, dim3(SD_THREADS), 0, c->stream, ta);
     else hipLaunchKernelGGL(stream_detect_kernel<false>, dgrid, dim3(SD_THREADS), 0, c->stream, ta);
     c->toc();
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(OFDM_E_HIP, "stream_detect_kernel launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess)
+        return set_error(OFDM_E_HIP, "%s launch: %s", det ? det->name : "stream_detect_kernel", hipGetErrorString(e));
     c->tic(OFDM_K_STREAM_SELECT);
     hipLaunchKernelGGL(stream_select_kernel<0>, dim3((unsigned)nblocks), dim3(SS_THREADS), 0, c->stream, sa);
     hipLaunchKernelGGL(stream_select_kernel<1>, dim3(1), dim3(SS_SCAN_THREADS), 0, c->stream, sa);
@@ -713,4 +709,15 @@ extern "C" int ofdm_receive_stream(ofdm_ctx *ctx, const void *d_samples, int64_t
     e = hipGetLastError();
     if (e != hipSuccess) return set_error(OFDM_E_HIP, "stream_decode_kernel launch: %s", hipGetErrorString(e));
     return OFDM_OK;
+}
+
+}  // namespace ofdm
+
+using namespace ofdm;
+
+extern "C" int ofdm_receive_stream(ofdm_ctx *ctx, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
+                                   int payload, int64_t max_packets, void *d_packets, void *d_count, void *d_bits,
+                                   void *d_eq, void *d_counters, void *d_metric, void *d_cross) {
+    return stream_receive(reinterpret_cast<Ctx *>(ctx), d_samples, n_samples, opts, payload, max_packets, d_packets,
+                          d_count, d_bits, d_eq, d_counters, d_metric, d_cross, nullptr);
 }

@@ -465,10 +465,13 @@ class Engine:
     def receive_stream(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
                        want_bits: bool = True, want_eq: bool = False, want_metric: bool = False,
                        want_cross: bool = False, counters=None, keep_device: bool = False,
-                       opts: dict | None = None) -> dict:
+                       opts: dict | None = None, detector: str = "reference", threshold: float = 0.75) -> dict:
         """Every packet of one recording of any length (ofdm_receive_stream, include/ofdm_mi355x_stream.h): the
         reference's detection rule once over the whole recording, then the receiver chain on every packet found.
         opts: single fields of ofdm_rx_opts over the mode's (abi.make_rx_opts; a stream has no cap_len to set).
+        detector, threshold: ofdm_receive_stream_ex's options (include/ofdm_mi355x_detect.h): "reference", the metric
+        above over Lc = n - 47 positions, or "conjugate", the lag-32 delay-and-correlate metric with the conjugate over
+        Lc = n - 63; a crossing is M > threshold, 0 < threshold < 1.  The defaults are ofdm_receive_stream itself.
 
         samples: a one-dimensional contiguous torch complex64 tensor on this engine's device, used in place (never
         written), or a numpy complex64 array, uploaded once.  Anything else raises ValueError before any launch.
@@ -476,7 +479,7 @@ class Engine:
         device tensor of NCOUNTERS elements, added to.
         Returns count (records written), found (packets in the stream), positions (int64 [count]), records (a
         structured host array, abi.stream_packet_dtype()), bits ([count, 96 D] int32), eq ([count, 48 D] complex64),
-        messages, metric (float32 [n - 47]) and cross (uint32 words, stream.unpack_cross) -- those not asked for None;
+        messages, metric (float32 [Lc]) and cross (uint32 words, stream.unpack_cross) -- those not asked for None;
         bits, eq, metric and cross stay on the device for torch input.  The call reads the packet count back, so it
         waits for the device.  keep_device: also return d_packets (uint8 [rows, 64]), d_count (int64 [2]) and d_words
         (int32 [rows, 3 D], None without want_bits), the device tensors the kernels wrote, for score_packets."""
@@ -509,9 +512,10 @@ class Engine:
             if not (torch.is_tensor(counters) and counters.dtype == torch.int64 and counters.device == dev
                     and counters.numel() == abi.NCOUNTERS and counters.is_contiguous()):
                 raise ValueError("counters must be a contiguous int64 device tensor of NCOUNTERS elements")
-        lc = max(n - 47, 0)
+        sopts = abi.make_stream_opts(detector, threshold)
+        lc = abi.stream_positions(n, detector)
         pk, cnt, words, eq, metric, cross = self._launch_receive_stream(
-            t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross, counters)
+            t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross, counters, sopts)
         found, count = (int(v) for v in cnt.cpu())
         records = pk[:count].cpu().numpy().view(abi.stream_packet_dtype()).reshape(count)
         bits = None
@@ -538,11 +542,12 @@ class Engine:
         return out
 
     def receive_stream_device(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
-                              counters=None) -> dict:
+                              counters=None, detector: str = "reference", threshold: float = 0.75) -> dict:
         """receive_stream for a device recording without the read-back: nothing waits for the device.  samples: a
         one-dimensional contiguous torch complex64 tensor on this engine's device.  Returns d_packets (uint8
         [rows, 64], ofdm_stream_packet), d_count (int64 [2]: found, written) and d_words (int32 [rows, 3 D]), of which
-        the first d_count[1] rows are written, and frames -- what score_packets takes."""
+        the first d_count[1] rows are written, and frames -- what score_packets takes.  detector, threshold: as
+        receive_stream's."""
         torch = _torch()
         opts = make_rx_opts(mode)
         nd = self.payload_frames(payload)
@@ -558,17 +563,21 @@ class Engine:
             max_packets = n // 301 + 1
         if int(max_packets) != max_packets or max_packets < 0:
             raise ValueError(f"max_packets must be a non-negative integer, got {max_packets!r}")
+        sopts = abi.make_stream_opts(detector, threshold)
         pk, cnt, words = self._launch_receive_stream(samples, opts, payload, nd, int(max_packets), True, False, False,
-                                                     False, counters)[:3]
+                                                     False, counters, sopts)[:3]
         return dict(d_packets=pk, d_count=cnt, d_words=words, frames=nd)
 
     def _launch_receive_stream(self, t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross,
-                               counters):
-        """Allocates ofdm_receive_stream's outputs and enqueues it: (packets, count, words, eq, metric, cross)"""
+                               counters, sopts=None):
+        """Allocates ofdm_receive_stream's outputs and enqueues it: (packets, count, words, eq, metric, cross).  sopts
+        (abi.StreamOpts) other than the defaults goes through ofdm_receive_stream_ex, its outputs sized by its Lc."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n = int(t.shape[0])
-        lc = max(n - 47, 0)
+        conj = sopts is not None and sopts.detector == abi.DETECTOR["conjugate"]
+        default = sopts is None or (not conj and sopts.threshold == abi.DETECT_THRESHOLD)
+        lc = abi.stream_positions(n, "conjugate" if conj else "reference")
         rows = max(max_packets, 1)                                    # a pointer even when nothing may be written
         pk = torch.empty((rows, C.sizeof(abi.StreamPacket)), dtype=torch.uint8, device=dev)
         cnt = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -577,9 +586,14 @@ class Engine:
         metric = torch.empty(max(lc, 1), dtype=torch.float32, device=dev) if want_metric else None
         cross = torch.empty(max((lc + 31) // 32, 1), dtype=torch.int32, device=dev) if want_cross else None
         opt = lambda x: None if x is None else _ptr(x)
-        check(self.lib, self.lib.ofdm_receive_stream(
-            self.ctx, _ptr(t) if n else None, n, C.byref(opts), abi.PAYLOAD[payload], max_packets, _ptr(pk), _ptr(cnt),
-            opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream")
+        if default:
+            check(self.lib, self.lib.ofdm_receive_stream(
+                self.ctx, _ptr(t) if n else None, n, C.byref(opts), abi.PAYLOAD[payload], max_packets, _ptr(pk), _ptr(cnt),
+                opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream")
+        else:
+            check(self.lib, self.lib.ofdm_receive_stream_ex(
+                self.ctx, _ptr(t) if n else None, n, C.byref(opts), C.byref(sopts), abi.PAYLOAD[payload], max_packets,
+                _ptr(pk), _ptr(cnt), opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream_ex")
         return pk, cnt, words, eq, metric, cross
 
     def impair_stream(self, x, power: float, snr_db: float, cfo_hz: float = 0.0, taps=None, noise: str = "real",

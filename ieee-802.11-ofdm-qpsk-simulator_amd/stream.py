@@ -5,7 +5,8 @@ select_packets() is the executable specification of include/ofdm_mi355x_stream.h
 (csrc/ofdm_stream.hip) are tested against it bit for bit; it is host code for tests and tools and is never on a hot
 path.  main() is `python ofdm_pkg.py stream`.  pack_messages() packs texts into the payload words both the receivers'
 d_bits and ofdm_transmit_packets' d_words use; transmit_main() is `python ofdm_pkg.py transmit`.  score_packets() is
-the executable specification of ofdm_score_packets (include/ofdm_mi355x_channel.h).
+the executable specification of ofdm_score_packets (include/ofdm_mi355x_channel.h).  detection_metric() and
+positions() are the executable specification of the two detectors of include/ofdm_mi355x_detect.h.
 """
 from __future__ import annotations
 
@@ -21,6 +22,39 @@ FRONT_GAP = 300           # a front's previous crossing is more than this far ba
 CONFIRM = 230             # the second look, front + 230 (OFDM.c:745-760)
 PACKET_OFFSET = 11        # len_RRC_rx + 1 (OFDM.c:758)
 LAST_FRONT = 4            # OFDM_STREAM_LAST_FRONT
+
+
+DETECTORS = {"reference": (16, False), "conjugate": (32, True)}     # lag, conjugate; the window is 32 for both
+
+
+def positions(n: int, detector: str = "reference") -> int:
+    """Lc, the detection positions of a stream of n samples (ofdm_stream_positions): n - 47 for the reference's
+    metric, n - 63 for the conjugate one, 0 when there are none."""
+    if detector not in DETECTORS:
+        raise ValueError(f"detector must be one of {tuple(DETECTORS)}, got {detector!r}")
+    return max(int(n) - 31 - DETECTORS[detector][0], 0)
+
+
+def detection_metric(x, detector: str = "reference") -> np.ndarray:
+    """The detection metric M[i], 0 <= i < positions(len(x), detector), in double precision; NaN where the power is
+    zero (no crossing).
+
+    reference  M = |sum_{k<32} r[i+k] r[i+k+16]|^2 / (sum_{k<32} |r[i+k+16]|^2)^2, no conjugate (OFDM.c:659-683)
+    conjugate  M = |sum_{k<32} r[i+k] conj(r[i+k+32])|^2 / (sum_{k<32} |r[i+k+32]|^2)^2: the short training field's
+               period at 40 MS/s; |c| does not see the channel's phase or a carrier offset
+
+    select_packets(M, thr) is the rest of either rule."""
+    x = np.asarray(x).astype(np.complex128).reshape(-1)
+    lc = positions(len(x), detector)
+    if lc == 0:
+        return np.zeros(0, np.float64)
+    lag, conj = DETECTORS[detector]
+    prod = x[:-lag] * (np.conj(x[lag:]) if conj else x[lag:])
+    # windows are summed directly (no running sum): an idle gap of exact zeros gives exactly zero power, hence NaN
+    c = np.lib.stride_tricks.sliding_window_view(prod, 32)[:lc].sum(axis=1)
+    p = np.lib.stride_tricks.sliding_window_view((x.real ** 2 + x.imag ** 2)[lag:], 32)[:lc].sum(axis=1)
+    with np.errstate(all="ignore"):
+        return (c.real ** 2 + c.imag ** 2) / (p * p)
 
 
 def unpack_cross(words, lc: int) -> np.ndarray:
@@ -203,7 +237,12 @@ def main(argv=None) -> int:
     ap.add_argument("--noise", default="real", choices=("real", "complex", "none"))
     ap.add_argument("--seed", type=int, default=0x80211A)
     ap.add_argument("--max-packets", type=int, default=None)
+    ap.add_argument("--detector", choices=tuple(DETECTORS), default="reference",
+                    help="the detection metric: the reference's, or delay-and-correlate with the conjugate at lag 32")
+    ap.add_argument("--threshold", type=float, default=THRESHOLD, help="a crossing is M > threshold, inside (0, 1)")
     a = ap.parse_args(argv)
+    if not 0.0 < a.threshold < 1.0:
+        raise SystemExit("--threshold must be inside (0, 1)")
     import torch  # noqa: PLC0415
     from . import abi  # noqa: PLC0415
     from .channel import make_stream, parse_taps  # noqa: PLC0415
@@ -222,7 +261,7 @@ def main(argv=None) -> int:
             gen.manual_seed(a.seed)
             samples = make_stream(w, synthetic_segments(len(w) // 10, a.frames, a.gap), a.snr, a.cfo_hz,
                                   taps=None if a.taps is None else parse_taps(a.taps), noise=a.noise, generator=gen)
-        out = eng.receive_stream(samples, max_packets=a.max_packets)
+        out = eng.receive_stream(samples, max_packets=a.max_packets, detector=a.detector, threshold=a.threshold)
     rec = out["records"]
     d = Path(a.out)
     d.mkdir(parents=True, exist_ok=True)
@@ -241,5 +280,5 @@ def main(argv=None) -> int:
     return 0
 
 
-__all__ = ["select_packets", "unpack_cross", "first_packet", "synthetic_segments", "main", "pack_messages",
+__all__ = ["select_packets", "detection_metric", "positions", "DETECTORS", "unpack_cross", "first_packet", "synthetic_segments", "main", "pack_messages",
            "transmit_main", "score_packets", "SCORE_MAX_WINDOW", "NSCORE", "MAX_DATA_SYMBOLS", "THRESHOLD", "FRONT_GAP", "CONFIRM", "PACKET_OFFSET", "LAST_FRONT"]

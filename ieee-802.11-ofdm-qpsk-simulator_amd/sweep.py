@@ -174,7 +174,8 @@ def captures_main(argv=None):
 
 
 def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: float = 0.0, taps=None,
-               noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=None, fading=None) -> dict:
+               noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=None, fading=None,
+               detector: str = "reference", threshold: float = 0.75) -> dict:
     """Packet-error and bit-error counts against SNR for packets that each carry their own bits, the recording never
     leaving the device: the packets (words: uint32 [n, 3 n_data], each behind `gap` idle samples, and a closing gap)
     are transmitted once; per SNR point q the clean recording is impaired into a second buffer with the noise stream
@@ -188,6 +189,10 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     refers to the realised mean received power per nominal packet sample, sum |clean|^2 / (n P); the default window
     grows to (8, 40 + L - 1), since the detection front moves with the channel's delay, and `gap` must cover it.  The
     static taps, cfo_hz and the noise apply afterwards as they do without fading.
+
+    detector, threshold: Engine.receive_stream_device's (include/ofdm_mi355x_detect.h).  The default window is the same
+    for both detectors: the conjugate detector's fronts are the reference's on an unfaded link, and under a selective
+    channel at low SNR a few of its detections can fall outside it and count as missed.
 
     Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
     import torch  # noqa: PLC0415
@@ -225,7 +230,7 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     for q, s in enumerate(snr):
         engine.impair_stream(clean, power, float(s), cfo_hz, taps=taps, noise=noise, seed=seed, trial=trial,
                              snr_index=q, out=rec)
-        rx = engine.receive_stream_device(rec)
+        rx = engine.receive_stream_device(rec, detector=detector, threshold=threshold)
         engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])
     return dict(snr_db=snr, totals=totals.cpu().numpy(), power=power, packets=n, samples=n_out)
 
@@ -266,8 +271,13 @@ def link_main(argv=None) -> int:
     ap.add_argument("--pdp", default=None, help="power delay profile of the fading channel: linear powers per 25 ns tap, "
                                                 "e.g. 1,0.5,0.25,0.125 (normalised to sum 1; implies --fading rayleigh)")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x80211A)
+    ap.add_argument("--detector", choices=tuple(abi.DETECTOR), default="reference",
+                    help="the detection metric: the reference's, or delay-and-correlate with the conjugate at lag 32")
+    ap.add_argument("--threshold", type=float, default=abi.DETECT_THRESHOLD, help="a crossing is M > threshold, inside (0, 1)")
     ap.add_argument("--out", default="data")
     a = ap.parse_args(argv)
+    if not 0.0 < a.threshold < 1.0:
+        raise SystemExit("--threshold must be inside (0, 1)")
     snr = parse_snr_grid(a.snr)
     fading = None
     if a.fading or a.pdp:
@@ -289,7 +299,7 @@ def link_main(argv=None) -> int:
     t0 = time.perf_counter()
     with Engine(0) as eng:
         res = link_sweep(eng, words, d, a.gap, snr, cfo_hz=a.cfo_hz, taps=None if a.taps is None else parse_taps(a.taps),
-                         noise=a.noise, seed=a.seed, fading=fading)
+                         noise=a.noise, seed=a.seed, fading=fading, detector=a.detector, threshold=a.threshold)
     wall = time.perf_counter() - t0
     t = res["totals"]
     ber = t[:, abi.S_BIT_ERR] / np.maximum(t[:, abi.S_BITS], 1)

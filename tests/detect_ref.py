@@ -1,0 +1,130 @@
+"""Helpers of tests/test_detect_host.py and tests/test_gpu_detect.py: the streams and the fading fixture of the
+detector tests (include/ofdm_mi355x_detect.h), host code in fp64, no GPU."""
+from __future__ import annotations
+
+import numpy as np
+
+GAP = 500
+PDP4 = np.exp(-np.arange(4.0)) / np.exp(-np.arange(4.0)).sum()       # four taps of profile e^-l, total power 1
+# The fading fixture's seed.  The conditions on it (test_detect_host.test_fading_fixture): the conjugate detector finds
+# all 60 packets and every one decodes without a bit error, the reference detector finds fewer than 60.  The first
+# seed tried, 0x80211A, meets them.
+FADE_SEED = 0x80211A
+FADE_PACKETS = 60
+TS = 25e-9                                                             # the recording's 40 MS/s
+
+
+def rand_words(d: int, n: int, seed: int) -> np.ndarray:
+    return np.random.default_rng(seed).integers(0, 1 << 32, (n, 3 * d), dtype=np.uint64).astype(np.uint32)
+
+
+def bits_of(words: np.ndarray) -> np.ndarray:
+    """[n, 96 D] int32, MSB first"""
+    w = np.asarray(words, np.uint32)
+    return ((w[..., None] >> np.arange(31, -1, -1, dtype=np.uint32)) & 1).astype(np.int32).reshape(len(w), -1)
+
+
+def packet_stream(oracle, words, taps=None, gap: int = GAP, cfo_hz: float = 0.0):
+    """Every row of words as one packet of the oracle's Transmitter() (one period), convolved with its row of taps,
+    each behind `gap` zeros, and a closing gap; rotated by cfo_hz over the stream index.  Returns the complex128
+    stream and the packets' first samples."""
+    bits = bits_of(words)
+    pk = [oracle.frame_waveform(b, "c", True, 1) for b in bits]
+    if taps is not None:
+        pk = [np.convolve(w, np.asarray(h, np.complex128)) for w, h in zip(pk, taps)]
+    stride = len(pk[0]) + gap
+    x = np.zeros(len(pk) * stride + gap, np.complex128)
+    pos = gap + stride * np.arange(len(pk))
+    for p, w in zip(pos, pk):
+        x[p:p + len(w)] = w
+    if cfo_hz:
+        x *= np.exp(2j * np.pi * cfo_hz * TS * np.arange(len(x)))
+    return x, pos.astype(np.int64)
+
+
+def add_noise(x, snr_db: float, n_packet_samples: int, seed: int) -> np.ndarray:
+    """complex noise over the whole stream, snr_db against the mean power of the packets' n_packet_samples samples"""
+    rng = np.random.default_rng(seed)
+    power = float((np.abs(x) ** 2).sum()) / n_packet_samples
+    s = np.sqrt(power / 10 ** (snr_db / 10) / 2)
+    return x + s * (rng.standard_normal(len(x)) + 1j * rng.standard_normal(len(x)))
+
+
+def fade_taps(n: int = FADE_PACKETS, seed: int = FADE_SEED) -> np.ndarray:
+    """Rayleigh taps of profile PDP4 for n packets from a fixed numpy generator: complex64 [n, 4]"""
+    rng = np.random.default_rng(seed)
+    z = rng.standard_normal((n, 4)) + 1j * rng.standard_normal((n, 4))
+    return (np.sqrt(PDP4 / 2) * z).astype(np.complex64)
+
+
+def fading_fixture(oracle):
+    """60 packets of 2 data symbols with payloads of their own, each through its own four taps, 500-sample gaps, no
+    noise: words, taps, the fp64 stream and the packets' first samples"""
+    words = rand_words(2, FADE_PACKETS, FADE_SEED + 1)
+    taps = fade_taps()
+    x, pos = packet_stream(oracle, words, taps)
+    return words, taps, x, pos
+
+
+def oracle_bit_errors(oracle, x, p: int, truth) -> int:
+    """the oracle's decode_at at stream position p (samples outside the stream read as zero)"""
+    nfr = 320 + 80 * (len(truth) // 96)
+    lo = p - 40
+    cap = np.zeros(2 * nfr + 100, np.complex128)
+    a, b = max(lo, 0), min(lo + len(cap), len(x))
+    cap[a - lo:b - lo] = x[a:b]
+    o = oracle.decode_at(cap, truth, p - lo, cap_len=len(cap))
+    return int((o["bits"] != np.asarray(truth)).sum())
+
+
+def noisy_stream(oracle, d: int, snr_db: float, cfo_hz: float, faded: bool, seed: int):
+    """About 3e4 samples -- more than three detection tiles -- of packets of d data symbols behind 500-sample gaps, each
+    through its own four taps when faded, under a carrier offset and complex noise: the complex64 stream and the
+    packets' first samples"""
+    plen = 2 * (320 + 80 * d) + 20
+    n = max(28000 // (plen + GAP), 4)
+    x, pos = packet_stream(oracle, rand_words(d, n, seed), fade_taps(n, seed + 1) if faded else None, cfo_hz=cfo_hz)
+    return add_noise(x, snr_db, n * plen, seed + 2).astype(np.complex64), pos
+
+
+# The streams of tests/test_gpu_detect.py: (D, SNR dB, CFO Hz, faded) -> seed.  The seed is 7000 + 100 D + 10 SNR + 2 q +
+# faded (q the CFO's index) plus 1000 per replacement: a stream whose fp64 metric has a front or confirmation decision
+# inside |M - 0.75| <= 0.75e-3 (band_is_harmless, checked again by test_detect_host) is replaced by the next seed,
+# since there the fp32 kernel may decide either way.
+CFOS = (0.0, 40e3, -90e3)
+STREAM_SEEDS = {(2, 14, 0.0, False): 7340, (2, 14, 0.0, True): 8341, (2, 14, 40e3, False): 8342, (2, 14, 40e3, True): 9343,
+                (2, 14, -90e3, False): 7344, (2, 14, -90e3, True): 7345, (2, 25, 0.0, False): 10450, (2, 25, 0.0, True): 7451,
+                (2, 25, 40e3, False): 7452, (2, 25, 40e3, True): 7453, (2, 25, -90e3, False): 7454, (2, 25, -90e3, True): 9455,
+                (15, 14, 0.0, False): 8640, (15, 14, 0.0, True): 8641, (15, 14, 40e3, False): 9642, (15, 14, 40e3, True): 8643,
+                (15, 14, -90e3, False): 8644, (15, 14, -90e3, True): 8645, (15, 25, 0.0, False): 8750, (15, 25, 0.0, True): 9751,
+                (15, 25, 40e3, False): 8752, (15, 25, 40e3, True): 8753, (15, 25, -90e3, False): 9754, (15, 25, -90e3, True): 8755}
+
+
+def band_positions(metric, thr: float, band: float) -> np.ndarray:
+    with np.errstate(invalid="ignore"):
+        return np.nonzero(np.abs(np.asarray(metric, np.float64) - thr) <= band)[0]
+
+
+def band_is_harmless(metric, thr: float, band: float) -> bool:
+    """No front or confirmation decision lies in the band |M - thr| <= band: select_packets gives the same packets
+    and flags when any one position of the band, or all of them, decide the other way."""
+    from ofdm_amd.stream import select_packets
+    m = np.asarray(metric, np.float64)
+    with np.errstate(invalid="ignore"):
+        cross = m > thr
+    want = select_packets(cross)
+    idx = band_positions(m, thr, band)
+    trials = [idx[k:k + 1] for k in range(len(idx))]
+    for flip in trials:
+        c = cross.copy()
+        c[flip] = ~c[flip]
+        got = select_packets(c)
+        if not (np.array_equal(got["positions"], want["positions"]) and np.array_equal(got["flags"], want["flags"])):
+            return False
+    for value in (False, True):
+        c = cross.copy()
+        c[idx] = value
+        got = select_packets(c)
+        if not (np.array_equal(got["positions"], want["positions"]) and np.array_equal(got["flags"], want["flags"])):
+            return False
+    return True
