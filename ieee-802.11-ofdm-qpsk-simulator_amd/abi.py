@@ -36,6 +36,7 @@ K_TRANSMIT = 7                                                   # OFDM_K_TRANSM
 K_CHANNEL, K_SCORE = 8, 9                                        # OFDM_K_CHANNEL, OFDM_K_SCORE (ofdm_mi355x_channel.h)
 K_FADE, K_DRAW_TAPS = 10, 11                                     # OFDM_K_FADE, OFDM_K_DRAW_TAPS (ofdm_mi355x_fading.h)
 K_STREAM_DETECT_CONJ = 12                                        # OFDM_K_STREAM_DETECT_CONJ (ofdm_mi355x_detect.h)
+K_STREAM_TIMING = 13                                             # OFDM_K_STREAM_TIMING (ofdm_mi355x_timing.h)
 
 # every entry point of the header, with ctypes argument types
 _V = C.c_void_p
@@ -152,6 +153,17 @@ DETECTOR = {"reference": 0, "conjugate": 1}      # OFDM_DETECT_REFERENCE, OFDM_D
 DETECT_THRESHOLD = 0.75                          # OFDM_DETECT_THRESHOLD
 DETECT_HALO = {"reference": 47, "conjugate": 63}  # Lc = n - halo
 
+# the extension header include/ofdm_mi355x_timing.h (fine timing for the stream receiver by cross-correlation against
+# the long training field); the export lists above and ABI_VERSION do not change with it
+TIMING_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_timing.h"
+_TIMING_SIGS = {
+    "ofdm_receive_stream_timed": (C.c_int, [_V, _V, C.c_int64, _V, _V, C.c_int, C.c_int, C.c_int64, _V, _V, _V, _V, _V, _V,
+                                            _V, _V]),
+}
+TIMING_EXPORTS = tuple(_TIMING_SIGS)
+TIMING = {"none": 0, "ltf": 1}                   # OFDM_TIMING_NONE, OFDM_TIMING_LTF
+TIMING_BACK, TIMING_FWD = 56, 8                  # OFDM_TIMING_BACK, OFDM_TIMING_FWD: shifts -56 .. +7
+
 
 class OfdmError(RuntimeError):
     pass
@@ -233,6 +245,24 @@ def stream_positions(n: int, detector: str = "reference") -> int:
     if detector not in DETECTOR:
         raise ValueError(f"detector must be one of {tuple(DETECTOR)}, got {detector!r}")
     return max(int(n) - DETECT_HALO[detector], 0)
+
+
+class StreamTiming(C.Structure):
+    """ofdm_stream_timing (16 bytes, one per record)"""
+    _fields_ = [("coarse_pos", C.c_int64), ("quality", C.c_float), ("shift", C.c_int32)]
+
+
+def stream_timing_dtype():
+    """numpy structured dtype of ofdm_stream_timing"""
+    import numpy as np  # noqa: PLC0415
+    return np.dtype([("coarse_pos", "<i8"), ("quality", "<f4"), ("shift", "<i4")])
+
+
+def timing_code(timing: str) -> int:
+    """OFDM_TIMING_* of "none" or "ltf"; ValueError for anything else"""
+    if not isinstance(timing, str) or timing not in TIMING:
+        raise ValueError(f"timing must be one of {tuple(TIMING)}, got {timing!r}")
+    return TIMING[timing]
 
 
 class StreamPacket(C.Structure):
@@ -344,7 +374,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
     for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS,
-                              **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS}.items():
+                              **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS, **_TIMING_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -23,6 +23,8 @@
 //     [p - 20, p + 2 nfr - 2] (2 nfr + 19 samples, zero outside the stream) and runs capture_rx_kernel's chain on it.
 // ofdm_receive_stream_ex (ofdm_stream_conj.hip) enters through stream_receive with a detector of its own
 // (ofdm_stream_detect.h): another detection launch, then the selection and decode launches of this file.
+// ofdm_receive_stream_timed (ofdm_stream_timing.hip) adds a refiner through the same door: one launch of its own
+// between stream_select_kernel<2> and stream_decode_kernel that rewrites packet_pos.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -594,7 +596,7 @@ static void stream_taps(float out[21]) {
 // with its own halo; everything after the bitmap -- selection, compaction, decode -- is the same launches either way.
 int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts, int payload,
                    int64_t max_packets, void *d_packets, void *d_count, void *d_bits, void *d_eq, void *d_counters,
-                   void *d_metric, void *d_cross, const StreamDetector *det) {
+                   void *d_metric, void *d_cross, const StreamDetector *det, const StreamRefiner *ref) {
     const int halo = det ? det->halo : 47;
     if (!c) return set_error(OFDM_E_ARG, "ctx is NULL");
     if (!opts) return set_error(OFDM_E_ARG, "opts is NULL");
@@ -649,6 +651,7 @@ int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_
     int rc = c->ensure(&c->d_scratch2, &c->cap_scratch2, total);
     if (rc) return rc;
     char *base = (char *)c->d_scratch2;
+    if (ref && max_packets > 0 && (rc = ref->prepare(ref, c))) return rc;
 
     DetArgs ta{};
     ta.x = (const float2 *)d_samples;
@@ -689,6 +692,20 @@ int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_
     e = hipGetLastError();
     if (e != hipSuccess) return set_error(OFDM_E_HIP, "stream_select_kernel launch: %s", hipGetErrorString(e));
     if (max_packets == 0) return OFDM_OK;
+
+    if (ref) {                                                       // between the selection and the decode
+        RefineArgs ra{};
+        ra.x = ta.x;
+        ra.n = n_samples;
+        ra.count = sa.count;
+        ra.pk = sa.pk;
+        ra.max_packets = max_packets;
+        c->tic(ref->kernel);
+        ref->launch(ref, c, c->stream, ra);
+        c->toc();
+        e = hipGetLastError();
+        if (e != hipSuccess) return set_error(OFDM_E_HIP, "%s launch: %s", ref->name, hipGetErrorString(e));
+    }
 
     da.x = ta.x;
     da.n = n_samples;

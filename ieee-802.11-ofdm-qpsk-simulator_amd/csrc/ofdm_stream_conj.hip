@@ -31,7 +31,7 @@ constexpr int CD_TILE = OFDM_STREAM_TILE;
 constexpr int CD_WORDS = CD_TILE / 32;
 static_assert(CD_TILE == CD_RUN * CD_THREADS && CD_TILE % 128 == 0 && (CD_RUN & 1), "tile = 256 odd runs, whole 16-byte groups of bitmap words");
 static_assert(sizeof(ofdm_stream_opts) == 32, "ofdm_stream_opts is 32 bytes");
-static_assert(OFDM_K_STREAM_DETECT_CONJ == Ctx::K_STREAM_DETECT_CONJ && Ctx::K_STREAM_DETECT_CONJ + 1 == Ctx::NK, "the next free timing id");
+static_assert(OFDM_K_STREAM_DETECT_CONJ == Ctx::K_STREAM_DETECT_CONJ && Ctx::K_STREAM_DETECT_CONJ < Ctx::NK, "the timing id of ofdm_mi355x_detect.h");
 
 template <bool CONJ>
 struct DetShape {
@@ -220,6 +220,42 @@ static void launch_thr(const StreamDetector *det, dim3 grid, hipStream_t stream,
     else hipLaunchKernelGGL(stream_detect_thr_kernel<false>, grid, dim3(CD_THREADS), 0, stream, a, det->threshold);
 }
 
+// ofdm_receive_stream_ex's body; ref (ofdm_stream_detect.h) is handed on to stream_receive
+int stream_receive_ex(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
+                      const ofdm_stream_opts *sopts, int payload, int64_t max_packets, void *d_packets, void *d_count,
+                      void *d_bits, void *d_eq, void *d_counters, void *d_metric, void *d_cross, const StreamRefiner *ref) {
+    int detector = OFDM_DETECT_REFERENCE;
+    float thr = OFDM_DETECT_THRESHOLD;
+    if (sopts) {
+        detector = sopts->detector;
+        thr = sopts->threshold;
+        if (detector != OFDM_DETECT_REFERENCE && detector != OFDM_DETECT_CONJUGATE)
+            return set_error(OFDM_E_ARG, "detector must be OFDM_DETECT_REFERENCE (0) or OFDM_DETECT_CONJUGATE (1), got %d", detector);
+        if (!(thr > 0.f && thr < 1.f)) return set_error(OFDM_E_ARG, "threshold must be inside (0, 1), got %g", (double)thr);
+        for (int k = 0; k < 6; ++k)
+            if (sopts->reserved[k]) return set_error(OFDM_E_ARG, "ofdm_stream_opts.reserved[%d] must be 0", k);
+    }
+    // the defaults are ofdm_receive_stream itself: the same instantiations, byte-identical outputs
+    if (detector == OFDM_DETECT_REFERENCE && thr == OFDM_DETECT_THRESHOLD)
+        return stream_receive(c, d_samples, n_samples, opts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
+                              d_counters, d_metric, d_cross, nullptr, ref);
+    StreamDetector det{};
+    det.threshold = thr;
+    if (detector == OFDM_DETECT_CONJUGATE) {
+        det.halo = DetShape<true>::HALO;
+        det.kernel = OFDM_K_STREAM_DETECT_CONJ;
+        det.launch = launch_conj;
+        det.name = "stream_detect_conj_kernel";
+    } else {
+        det.halo = DetShape<false>::HALO;
+        det.kernel = OFDM_K_STREAM_DETECT;
+        det.launch = launch_thr;
+        det.name = "stream_detect_thr_kernel";
+    }
+    return stream_receive(c, d_samples, n_samples, opts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
+                          d_counters, d_metric, d_cross, &det, ref);
+}
+
 }  // namespace ofdm
 
 using namespace ofdm;
@@ -235,35 +271,6 @@ extern "C" int ofdm_receive_stream_ex(ofdm_ctx *ctx, const void *d_samples, int6
                                       const ofdm_stream_opts *sopts, int payload, int64_t max_packets, void *d_packets,
                                       void *d_count, void *d_bits, void *d_eq, void *d_counters, void *d_metric,
                                       void *d_cross) {
-    int detector = OFDM_DETECT_REFERENCE;
-    float thr = OFDM_DETECT_THRESHOLD;
-    if (sopts) {
-        detector = sopts->detector;
-        thr = sopts->threshold;
-        if (detector != OFDM_DETECT_REFERENCE && detector != OFDM_DETECT_CONJUGATE)
-            return set_error(OFDM_E_ARG, "detector must be OFDM_DETECT_REFERENCE (0) or OFDM_DETECT_CONJUGATE (1), got %d", detector);
-        if (!(thr > 0.f && thr < 1.f)) return set_error(OFDM_E_ARG, "threshold must be inside (0, 1), got %g", (double)thr);
-        for (int k = 0; k < 6; ++k)
-            if (sopts->reserved[k]) return set_error(OFDM_E_ARG, "ofdm_stream_opts.reserved[%d] must be 0", k);
-    }
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    // the defaults are ofdm_receive_stream itself: the same instantiations, byte-identical outputs
-    if (detector == OFDM_DETECT_REFERENCE && thr == OFDM_DETECT_THRESHOLD)
-        return stream_receive(c, d_samples, n_samples, opts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
-                              d_counters, d_metric, d_cross, nullptr);
-    StreamDetector det{};
-    det.threshold = thr;
-    if (detector == OFDM_DETECT_CONJUGATE) {
-        det.halo = DetShape<true>::HALO;
-        det.kernel = OFDM_K_STREAM_DETECT_CONJ;
-        det.launch = launch_conj;
-        det.name = "stream_detect_conj_kernel";
-    } else {
-        det.halo = DetShape<false>::HALO;
-        det.kernel = OFDM_K_STREAM_DETECT;
-        det.launch = launch_thr;
-        det.name = "stream_detect_thr_kernel";
-    }
-    return stream_receive(c, d_samples, n_samples, opts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
-                          d_counters, d_metric, d_cross, &det);
+    return stream_receive_ex(reinterpret_cast<Ctx *>(ctx), d_samples, n_samples, opts, sopts, payload, max_packets, d_packets,
+                             d_count, d_bits, d_eq, d_counters, d_metric, d_cross, nullptr);
 }

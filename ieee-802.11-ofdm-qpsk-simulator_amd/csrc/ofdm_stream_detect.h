@@ -1,11 +1,12 @@
-// ofdm_stream_detect.h -- what ofdm_stream.hip (ofdm_receive_stream) and ofdm_stream_conj.hip (ofdm_receive_stream_ex)
-// share: the detection kernels' argument block and the hook through which the extended entry point replaces the
-// detection launch alone.  The selection and decode kernels stay in ofdm_stream.hip
+// ofdm_stream_detect.h -- what ofdm_stream.hip (ofdm_receive_stream), ofdm_stream_conj.hip (ofdm_receive_stream_ex) and
+// ofdm_stream_timing.hip (ofdm_receive_stream_timed) share: the detection kernels' argument block, the hook through
+// which the extended entry point replaces the detection launch alone, and the hook through which the timed one adds a
+// launch between the selection and the decode.  The selection and decode kernels stay in ofdm_stream.hip
 // and are launched from there (stream_receive), so their certified builds do not move and nothing of them is restated.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "ofdm_mi355x_stream.h"
+#include "ofdm_mi355x_detect.h"
 
 namespace ofdm {
 
@@ -30,10 +31,36 @@ struct StreamDetector {
     const char *name;              // for the launch error's text
 };
 
-// ofdm_receive_stream's body; det == nullptr is the reference's rule with stream_detect_kernel, bit for bit what the
-// entry point enqueued before the hook existed.
+// What a refiner's launch works on: the recording, and the records stream_select_kernel<2> has just written.
+struct RefineArgs {
+    const float2 *x;
+    int64_t n;
+    const int64_t *count;          // d_count: [1] records written
+    ofdm_stream_packet *pk;
+    int64_t max_packets;
+};
+
+// A launch between the selection and the decode (ofdm_stream_timing.hip: the fine timing of ofdm_receive_stream_timed)
+// that may rewrite packet_pos of the first d_count[1] records, under the timing id `kernel`; the decode kernel then
+// runs on what it left.  Not launched when max_packets is 0 or the stream has no positions.
+struct StreamRefiner {
+    int kernel;                    // ofdm_timing_query id of the launch
+    int (*prepare)(const StreamRefiner *ref, Ctx *c);   // after every argument check, before the first launch; an OFDM_E_* code
+    void (*launch)(const StreamRefiner *ref, Ctx *c, hipStream_t stream, const RefineArgs &a);
+    const char *name;              // for the launch error's text
+    void *out;                     // the refiner's own output (optional)
+};
+
+// ofdm_receive_stream's body; det == nullptr is the reference's rule with stream_detect_kernel, and ref == nullptr no
+// launch between the selection and the decode: with both, bit for bit what the entry point enqueued before the hooks
+// existed.
 int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts, int payload,
                    int64_t max_packets, void *d_packets, void *d_count, void *d_bits, void *d_eq, void *d_counters,
-                   void *d_metric, void *d_cross, const StreamDetector *det);
+                   void *d_metric, void *d_cross, const StreamDetector *det, const StreamRefiner *ref = nullptr);
+
+// ofdm_receive_stream_ex's body (ofdm_stream_conj.hip): sopts checked and turned into a detector, then stream_receive
+int stream_receive_ex(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
+                      const ofdm_stream_opts *sopts, int payload, int64_t max_packets, void *d_packets, void *d_count,
+                      void *d_bits, void *d_eq, void *d_counters, void *d_metric, void *d_cross, const StreamRefiner *ref);
 
 }  // namespace ofdm

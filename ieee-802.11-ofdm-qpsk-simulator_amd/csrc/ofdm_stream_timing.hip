@@ -1,0 +1,201 @@
+// ofdm_stream_timing.hip -- fine timing for the stream receiver (include/ofdm_mi355x_timing.h:
+// ofdm_receive_stream_timed).  A translation unit of its own: ofdm_stream.hip and ofdm_stream_conj.hip keep their
+// kernels as they are; this file adds one kernel and hands it to stream_receive as a refiner (ofdm_stream_detect.h),
+// which launches it between stream_select_kernel<2> and stream_decode_kernel.
+//
+//   stream_timing_kernel : one wave per packet, TM_WAVES waves per block, looping over d_count; lane j is candidate j
+//     (shift j - 56).  The wave stages the 319 samples [p + 322, p + 640] of the search window as real and imaginary
+//     planes in LDS, so lane j reads its 256 samples at plane index j + m: stride 1 across the lanes, no bank
+//     conflict.  The template is a kernel argument, wave-uniform: its operands come through the scalar cache into
+//     SGPRs, never through a per-lane load.  Per lane and packet: 8 segments of 32 complex multiply-adds
+//     x conj(t) -- four fused multiply-adds each, ascending k -- then L += |segment|^2, ascending s.  The order is fixed
+//     per packet, so L, the choice and the quality depend on nothing but the packet's own samples.
+//     The largest L with the smallest j is found by a 64-lane butterfly on (L, j); lanes 0..7 then sum the chosen
+//     window's power per segment for the quality, lane 0 writes packet_pos and the timing row.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+#include "ofdm_mi355x_timing.h"
+#include "ofdm_ctx.h"
+#include "ofdm_stream_detect.h"
+
+namespace ofdm {
+
+constexpr int TM_WAVES = 4;                                   // packets per block and sweep
+constexpr int TM_CAND = OFDM_TIMING_BACK + OFDM_TIMING_FWD;   // 64: one candidate per lane
+constexpr int TM_LTF = 394;                                   // 2 * 192 + 10: the first long training symbol in the waveform
+constexpr int TM_FIRST = TM_LTF - 16 - OFDM_TIMING_BACK;      // 322: candidate 0 reads from p + 322
+constexpr int TM_LEN = 256, TM_SEG = 32, TM_NSEG = TM_LEN / TM_SEG, TM_PERIOD = 128;
+constexpr int TM_WINDOW = TM_CAND - 1 + TM_LEN;               // 319 samples staged per packet
+constexpr int TM_PLANE = 320;
+constexpr int TM_LOADS = (TM_WINDOW + 63) / 64;
+static_assert(TM_CAND == 64, "lane = candidate");
+static_assert(TM_FIRST == 322 && TM_FIRST + TM_WINDOW - 1 == 640, "the search window is [p + 322, p + 640]");
+static_assert(TM_WINDOW <= TM_PLANE && (TM_CAND - 1) + (TM_LEN - 1) < TM_WINDOW, "every lane's last sample is staged");
+static_assert(sizeof(ofdm_stream_timing) == 16, "ofdm_stream_timing is 16 bytes");
+static_assert(OFDM_K_STREAM_TIMING == Ctx::K_STREAM_TIMING && Ctx::K_STREAM_TIMING + 1 == Ctx::NK, "the next free timing id");
+
+struct TimArgs {
+    const float2 *x;
+    int64_t n;
+    const int64_t *count;          // d_count: [1] records to refine
+    ofdm_stream_packet *pk;
+    ofdm_stream_timing *out;       // optional
+    float te[TM_NSEG];             // sum_k |t[32 s + k]|^2
+    float2 t[TM_PERIOD];           // the template's period: t[k] = P[k mod 128]
+};
+
+// LDS ordering between the lanes of one wave (the block's other waves run other packets)
+__device__ __forceinline__ void tm_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(64 * TM_WAVES) void stream_timing_kernel(TimArgs a) {
+    __shared__ float planes[TM_WAVES][2][TM_PLANE];
+    __shared__ float power[TM_WAVES][TM_NSEG];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    float *re = planes[wave][0], *im = planes[wave][1];
+    const int64_t cnt = a.count[1];
+    for (int64_t i = (int64_t)blockIdx.x * TM_WAVES + wave; i < cnt; i += (int64_t)gridDim.x * TM_WAVES) {
+        ofdm_stream_packet *pkt = a.pk + i;
+        const int64_t pv = pkt->packet_pos;
+        const int64_t p = ((int64_t)__builtin_amdgcn_readfirstlane((int)(pv >> 32)) << 32) |
+                          (uint32_t)__builtin_amdgcn_readfirstlane((int)pv);
+        int shift = 0;
+        float quality = 0.f;
+        // the whole search window inside the stream, or the packet keeps its position (wave-uniform)
+        if (p + TM_FIRST >= 0 && p + TM_FIRST + TM_WINDOW - 1 < a.n) {
+            const float2 *row = a.x + (p + TM_FIRST);
+            float2 v[TM_LOADS];
+#pragma unroll
+            for (int r = 0; r < TM_LOADS; ++r) {
+                const int m = lane + 64 * r;
+                v[r] = m < TM_WINDOW ? row[m] : make_float2(0.f, 0.f);
+            }
+#pragma unroll
+            for (int r = 0; r < TM_LOADS; ++r) {
+                const int m = lane + 64 * r;
+                if (m < TM_PLANE) { re[m] = v[r].x; im[m] = v[r].y; }
+            }
+            tm_wave_sync();
+            // ---- L[lane]: 8 segments of 32 terms x conj(t) ----
+            float lam = 0.f;
+#pragma unroll 1
+            for (int s = 0; s < TM_NSEG; ++s) {
+                const float *xr = re + lane + TM_SEG * s, *xi = im + lane + TM_SEG * s;
+                const float2 *t = a.t + ((TM_SEG * s) & (TM_PERIOD - 1));
+                float cx = 0.f, cy = 0.f;
+#pragma unroll
+                for (int k = 0; k < TM_SEG; ++k) {
+                    const float ur = xr[k], ui = xi[k], tr = t[k].x, ti = t[k].y;
+                    cx = fmaf(ur, tr, cx); cx = fmaf(ui, ti, cx);
+                    cy = fmaf(ui, tr, cy); cy = fmaf(-ur, ti, cy);
+                }
+                lam = fmaf(cx, cx, lam);
+                lam = fmaf(cy, cy, lam);
+            }
+            // ---- the largest L, the smallest candidate among equals ----
+            float best = lam;
+            int bj = lane;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const float ov = __shfl_xor(best, o, 64);
+                const int oj = __shfl_xor(bj, o, 64);
+                if (ov > best || (ov == best && oj < bj)) { best = ov; bj = oj; }
+            }
+            bj = __builtin_amdgcn_readfirstlane(bj);
+            const float lbest = __shfl(lam, bj, 64);
+            if (lbest > 0.f) {                                          // wave-uniform
+                // ---- the chosen window's power per segment, then the quality ----
+                if (lane < TM_NSEG) {
+                    const float *xr = re + bj + TM_SEG * lane, *xi = im + bj + TM_SEG * lane;
+                    float e = 0.f;
+#pragma unroll 8
+                    for (int k = 0; k < TM_SEG; ++k) { e = fmaf(xr[k], xr[k], e); e = fmaf(xi[k], xi[k], e); }
+                    power[wave][lane] = e;
+                }
+                tm_wave_sync();
+                float den = 0.f;
+#pragma unroll
+                for (int s = 0; s < TM_NSEG; ++s) den = fmaf(a.te[s], power[wave][s], den);
+                quality = lbest / den;
+                shift = bj - OFDM_TIMING_BACK;
+            }
+            tm_wave_sync();                                             // the next packet overwrites the planes
+        }
+        if (lane == 0) {
+            if (shift) pkt->packet_pos = p + shift;
+            if (a.out) {
+                ofdm_stream_timing *o = a.out + i;
+                o->coarse_pos = p;
+                o->quality = quality;
+                o->shift = shift;
+            }
+        }
+    }
+}
+
+// w[394 .. 522) of the context's own Transmitter() waveform (frame_wave_kernel through ofdm_transmitter), once
+static int timing_prepare(const StreamRefiner *, Ctx *c) {
+    if (c->ltf_ready) return OFDM_OK;
+    std::vector<float2> w(10 * (2 * (320 + 80 * LONG_MAX_FRAMES) + 20));
+    int32_t len = 0;
+    int rc = ofdm_transmitter(reinterpret_cast<ofdm_ctx *>(c), OFDM_CONV_C, OFDM_PAYLOAD_MESSAGE, 1,
+                              reinterpret_cast<float *>(w.data()), (int32_t)w.size(), &len);
+    if (rc) return rc;
+    if (len < TM_LTF + TM_PERIOD) return set_error(OFDM_E_HIP, "Transmitter() gave %d samples, the template needs %d", len, TM_LTF + TM_PERIOD);
+    std::copy(w.begin() + TM_LTF, w.begin() + TM_LTF + TM_PERIOD, c->ltf_template);
+    c->ltf_ready = true;
+    return OFDM_OK;
+}
+
+static void timing_launch(const StreamRefiner *ref, Ctx *c, hipStream_t stream, const RefineArgs &r) {
+    TimArgs a{};
+    a.x = r.x;
+    a.n = r.n;
+    a.count = r.count;
+    a.pk = r.pk;
+    a.out = (ofdm_stream_timing *)ref->out;
+    std::copy(c->ltf_template, c->ltf_template + TM_PERIOD, a.t);
+    for (int s = 0; s < TM_NSEG; ++s) {
+        double e = 0.0;
+        for (int k = 0; k < TM_SEG; ++k) {
+            const float2 v = a.t[(TM_SEG * s + k) & (TM_PERIOD - 1)];
+            e += (double)v.x * v.x + (double)v.y * v.y;
+        }
+        a.te[s] = (float)e;
+    }
+    // the packet count stays on the device: enough blocks for max_packets, at most eight per CU; the waves loop
+    const int64_t blocks = (r.max_packets + TM_WAVES - 1) / TM_WAVES;
+    const dim3 grid((unsigned)std::min<int64_t>(blocks, 8 * (int64_t)c->cus));
+    hipLaunchKernelGGL(stream_timing_kernel, grid, dim3(64 * TM_WAVES), 0, stream, a);
+}
+
+}  // namespace ofdm
+
+using namespace ofdm;
+
+extern "C" int ofdm_receive_stream_timed(ofdm_ctx *ctx, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
+                                         const ofdm_stream_opts *sopts, int timing, int payload, int64_t max_packets,
+                                         void *d_packets, void *d_count, void *d_bits, void *d_eq, void *d_counters,
+                                         void *d_metric, void *d_cross, void *d_timing) {
+    if (timing != OFDM_TIMING_NONE && timing != OFDM_TIMING_LTF)
+        return set_error(OFDM_E_ARG, "timing must be OFDM_TIMING_NONE (0) or OFDM_TIMING_LTF (1), got %d", timing);
+    if (timing == OFDM_TIMING_NONE && d_timing)
+        return set_error(OFDM_E_ARG, "d_timing needs OFDM_TIMING_LTF: timing is OFDM_TIMING_NONE");
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    // no timing is ofdm_receive_stream_ex itself: the same launches, byte-identical outputs
+    if (timing == OFDM_TIMING_NONE)
+        return stream_receive_ex(c, d_samples, n_samples, opts, sopts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
+                                 d_counters, d_metric, d_cross, nullptr);
+    StreamRefiner ref{};
+    ref.kernel = OFDM_K_STREAM_TIMING;
+    ref.prepare = timing_prepare;
+    ref.launch = timing_launch;
+    ref.name = "stream_timing_kernel";
+    ref.out = d_timing;
+    return stream_receive_ex(c, d_samples, n_samples, opts, sopts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
+                             d_counters, d_metric, d_cross, &ref);
+}

@@ -465,13 +465,18 @@ class Engine:
     def receive_stream(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
                        want_bits: bool = True, want_eq: bool = False, want_metric: bool = False,
                        want_cross: bool = False, counters=None, keep_device: bool = False,
-                       opts: dict | None = None, detector: str = "reference", threshold: float = 0.75) -> dict:
+                       opts: dict | None = None, detector: str = "reference", threshold: float = 0.75,
+                       timing: str = "none") -> dict:
         """Every packet of one recording of any length (ofdm_receive_stream, include/ofdm_mi355x_stream.h): the
         reference's detection rule once over the whole recording, then the receiver chain on every packet found.
         opts: single fields of ofdm_rx_opts over the mode's (abi.make_rx_opts; a stream has no cap_len to set).
         detector, threshold: ofdm_receive_stream_ex's options (include/ofdm_mi355x_detect.h): "reference", the metric
         above over Lc = n - 47 positions, or "conjugate", the lag-32 delay-and-correlate metric with the conjugate over
         Lc = n - 63; a crossing is M > threshold, 0 < threshold < 1.  The defaults are ofdm_receive_stream itself.
+        timing: "none", or "ltf" (ofdm_receive_stream_timed, include/ofdm_mi355x_timing.h): every packet_pos is refined
+        against the long training field before the decode (stream.refine_timing is the rule); the result then also
+        holds coarse_pos (int64 [count], front + 11), shift (int32, packet_pos - coarse_pos) and quality (float32,
+        in [0, 1], 0 for a packet that was not refined) -- all three None with "none".
 
         samples: a one-dimensional contiguous torch complex64 tensor on this engine's device, used in place (never
         written), or a numpy complex64 array, uploaded once.  Anything else raises ValueError before any launch.
@@ -513,9 +518,10 @@ class Engine:
                     and counters.numel() == abi.NCOUNTERS and counters.is_contiguous()):
                 raise ValueError("counters must be a contiguous int64 device tensor of NCOUNTERS elements")
         sopts = abi.make_stream_opts(detector, threshold)
+        tcode = abi.timing_code(timing)
         lc = abi.stream_positions(n, detector)
-        pk, cnt, words, eq, metric, cross = self._launch_receive_stream(
-            t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross, counters, sopts)
+        pk, cnt, words, eq, metric, cross, tim = self._launch_receive_stream(
+            t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross, counters, sopts, tcode)
         found, count = (int(v) for v in cnt.cpu())
         records = pk[:count].cpu().numpy().view(abi.stream_packet_dtype()).reshape(count)
         bits = None
@@ -536,18 +542,24 @@ class Engine:
             metric = None if metric is None else metric.cpu().numpy()
             cross = None if cross is None else cross.cpu().numpy().view(np.uint32)
         out = dict(count=count, found=found, positions=records["packet_pos"].copy(), records=records, bits=bits,
-                   eq=eq, messages=messages, metric=metric, cross=cross, frames=nd)
+                   eq=eq, messages=messages, metric=metric, cross=cross, frames=nd, coarse_pos=None, shift=None,
+                   quality=None)
+        if tim is not None:
+            rows = tim[:count].cpu().numpy().view(abi.stream_timing_dtype()).reshape(count)
+            out.update(coarse_pos=rows["coarse_pos"].copy(), shift=rows["shift"].copy(), quality=rows["quality"].copy())
         if keep_device:
-            out.update(d_packets=pk, d_count=cnt, d_words=words)
+            out.update(d_packets=pk, d_count=cnt, d_words=words, d_timing=tim)
         return out
 
     def receive_stream_device(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
-                              counters=None, detector: str = "reference", threshold: float = 0.75) -> dict:
+                              counters=None, detector: str = "reference", threshold: float = 0.75,
+                              timing: str = "none") -> dict:
         """receive_stream for a device recording without the read-back: nothing waits for the device.  samples: a
         one-dimensional contiguous torch complex64 tensor on this engine's device.  Returns d_packets (uint8
         [rows, 64], ofdm_stream_packet), d_count (int64 [2]: found, written) and d_words (int32 [rows, 3 D]), of which
         the first d_count[1] rows are written, and frames -- what score_packets takes.  detector, threshold: as
-        receive_stream's."""
+        receive_stream's.  timing: as receive_stream's; d_timing (uint8 [rows, 16], ofdm_stream_timing) with "ltf", else
+        None."""
         torch = _torch()
         opts = make_rx_opts(mode)
         nd = self.payload_frames(payload)
@@ -564,14 +576,15 @@ class Engine:
         if int(max_packets) != max_packets or max_packets < 0:
             raise ValueError(f"max_packets must be a non-negative integer, got {max_packets!r}")
         sopts = abi.make_stream_opts(detector, threshold)
-        pk, cnt, words = self._launch_receive_stream(samples, opts, payload, nd, int(max_packets), True, False, False,
-                                                     False, counters, sopts)[:3]
-        return dict(d_packets=pk, d_count=cnt, d_words=words, frames=nd)
+        out = self._launch_receive_stream(samples, opts, payload, nd, int(max_packets), True, False, False, False,
+                                          counters, sopts, abi.timing_code(timing))
+        return dict(d_packets=out[0], d_count=out[1], d_words=out[2], frames=nd, d_timing=out[6])
 
     def _launch_receive_stream(self, t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross,
-                               counters, sopts=None):
-        """Allocates ofdm_receive_stream's outputs and enqueues it: (packets, count, words, eq, metric, cross).  sopts
-        (abi.StreamOpts) other than the defaults goes through ofdm_receive_stream_ex, its outputs sized by its Lc."""
+                               counters, sopts=None, timing=0):
+        """Allocates ofdm_receive_stream's outputs and enqueues it: (packets, count, words, eq, metric, cross, timing).
+        sopts (abi.StreamOpts) other than the defaults goes through ofdm_receive_stream_ex, its outputs sized by its Lc;
+        a timing other than OFDM_TIMING_NONE through ofdm_receive_stream_timed, with its rows (uint8 [rows, 16])."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n = int(t.shape[0])
@@ -586,7 +599,14 @@ class Engine:
         metric = torch.empty(max(lc, 1), dtype=torch.float32, device=dev) if want_metric else None
         cross = torch.empty(max((lc + 31) // 32, 1), dtype=torch.int32, device=dev) if want_cross else None
         opt = lambda x: None if x is None else _ptr(x)
-        if default:
+        tim = None
+        if timing != abi.TIMING["none"]:
+            tim = torch.empty((rows, C.sizeof(abi.StreamTiming)), dtype=torch.uint8, device=dev)
+            check(self.lib, self.lib.ofdm_receive_stream_timed(
+                self.ctx, _ptr(t) if n else None, n, C.byref(opts), None if sopts is None else C.byref(sopts), timing,
+                abi.PAYLOAD[payload], max_packets, _ptr(pk), _ptr(cnt), opt(words), opt(eq), opt(counters), opt(metric),
+                opt(cross), _ptr(tim)), "receive_stream_timed")
+        elif default:
             check(self.lib, self.lib.ofdm_receive_stream(
                 self.ctx, _ptr(t) if n else None, n, C.byref(opts), abi.PAYLOAD[payload], max_packets, _ptr(pk), _ptr(cnt),
                 opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream")
@@ -594,7 +614,7 @@ class Engine:
             check(self.lib, self.lib.ofdm_receive_stream_ex(
                 self.ctx, _ptr(t) if n else None, n, C.byref(opts), C.byref(sopts), abi.PAYLOAD[payload], max_packets,
                 _ptr(pk), _ptr(cnt), opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream_ex")
-        return pk, cnt, words, eq, metric, cross
+        return pk, cnt, words, eq, metric, cross, tim
 
     def impair_stream(self, x, power: float, snr_db: float, cfo_hz: float = 0.0, taps=None, noise: str = "real",
                       seed: int = 0x80211A, trial: int = 0, snr_index: int = 0, index0: int = 0, lead: int = 0,

@@ -100,6 +100,65 @@ def select_packets(cross_or_metric, thr: float = THRESHOLD) -> dict:
     return dict(fronts=fronts, confirmed=conf, positions=pos.astype(np.int64), flags=flags)
 
 
+TIMINGS = ("none", "ltf")
+LTF_START = 394           # 2 * 192 + 10: the first long training symbol in one period of Transmitter()'s waveform
+TIMING_BACK = 56          # OFDM_TIMING_BACK: candidate j is the shift j - 56
+TIMING_FWD = 8            # OFDM_TIMING_FWD
+TIMING_CANDIDATES = TIMING_BACK + TIMING_FWD
+TIMING_FIRST = LTF_START - 16 - TIMING_BACK     # 322: candidate 0 reads from p + 322
+TIMING_SPAN = TIMING_FIRST + TIMING_CANDIDATES - 1 + 256 - 1    # 640: the last sample a packet's search reads is p + 640
+TIMING_SEGMENT = 32       # the non-coherent segments: the short training field's period
+
+
+def ltf_template(wave) -> np.ndarray:
+    """The 256-sample template of the fine timing rule (include/ofdm_mi355x_timing.h) from one period of
+    Transmitter()'s 40 MS/s waveform: t[k] = wave[394 + (k mod 128)], the first long training symbol, which is cyclic
+    on both sides and does not depend on the payload or on the number of data symbols.  complex128 [256]."""
+    w = np.asarray(wave).astype(np.complex128).reshape(-1)
+    if len(w) < LTF_START + 128:
+        raise ValueError(f"a waveform of at least {LTF_START + 128} samples expected, got {len(w)}")
+    return np.tile(w[LTF_START:LTF_START + 128], 2)
+
+
+def refine_timing(x, positions, template) -> dict:
+    """The fine timing rule in double precision, the executable specification of ofdm_receive_stream_timed with
+    OFDM_TIMING_LTF: every coarse packet_pos p is moved to p - 56 + argmax_j L[j] over the 64 candidates j (the
+    smallest j wins a tie), where candidate j reads 256 samples from q = p + 322 + j and
+        L[j] = sum_{s<8} | sum_{k<32} x[q + 32 s + k] conj(t[32 s + k]) |^2 .
+    A packet whose search window [p + 322, p + 640] does not lie inside the stream, or whose every L[j] is 0, keeps p
+    with shift 0 and quality 0.  quality = L[j*] / sum_s (sum_k |t[32 s + k]|^2 sum_k |x[q* + 32 s + k]|^2), inside
+    [0, 1] and invariant to the scale of x and of t.
+
+    Returns positions (int64, refined), coarse (int64), shift (int32), quality (float64) and metric (float64
+    [n, 64], L; zeros for a packet that was not refined)."""
+    x = np.asarray(x).astype(np.complex128).reshape(-1)
+    t = np.asarray(template).astype(np.complex128).reshape(-1)
+    if len(t) != 256:
+        raise ValueError(f"a template of 256 samples expected (ltf_template), got {len(t)}")
+    coarse = np.asarray(positions, np.int64).reshape(-1)
+    n, m = len(x), len(coarse)
+    pos, shift = coarse.copy(), np.zeros(m, np.int32)
+    quality, metric = np.zeros(m, np.float64), np.zeros((m, TIMING_CANDIDATES), np.float64)
+    tc = np.conj(t).reshape(8, TIMING_SEGMENT)
+    te = (np.abs(t) ** 2).reshape(8, TIMING_SEGMENT).sum(axis=1)
+    for i, p in enumerate(coarse):
+        p = int(p)
+        if p + TIMING_FIRST < 0 or p + TIMING_SPAN >= n:
+            continue
+        win = np.lib.stride_tricks.sliding_window_view(x[p + TIMING_FIRST:p + TIMING_SPAN + 1], 256)    # [64, 256]
+        seg = (win.reshape(TIMING_CANDIDATES, 8, TIMING_SEGMENT) * tc).sum(axis=2)
+        lam = (seg.real ** 2 + seg.imag ** 2).sum(axis=1)
+        metric[i] = lam
+        j = int(np.argmax(lam))
+        if not lam[j] > 0.0:
+            continue
+        xe = (np.abs(win[j]) ** 2).reshape(8, TIMING_SEGMENT).sum(axis=1)
+        pos[i] = p - TIMING_BACK + j
+        shift[i] = j - TIMING_BACK
+        quality[i] = lam[j] / float((te * xe).sum())
+    return dict(positions=pos, coarse=coarse, shift=shift, quality=quality, metric=metric)
+
+
 def first_packet(sel: dict) -> int:
     """Packet_Selection's answer from select_packets': the first packet that is not the last front's, 0 when none."""
     keep = sel["positions"][sel["flags"] & LAST_FRONT == 0]
@@ -240,6 +299,9 @@ def main(argv=None) -> int:
     ap.add_argument("--detector", choices=tuple(DETECTORS), default="reference",
                     help="the detection metric: the reference's, or delay-and-correlate with the conjugate at lag 32")
     ap.add_argument("--threshold", type=float, default=THRESHOLD, help="a crossing is M > threshold, inside (0, 1)")
+    ap.add_argument("--timing", choices=TIMINGS, default="none",
+                    help="ltf: refine every packet's position against the long training field before the decode "
+                         "(packets.csv then has a coarse_pos column)")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:
         raise SystemExit("--threshold must be inside (0, 1)")
@@ -261,18 +323,21 @@ def main(argv=None) -> int:
             gen.manual_seed(a.seed)
             samples = make_stream(w, synthetic_segments(len(w) // 10, a.frames, a.gap), a.snr, a.cfo_hz,
                                   taps=None if a.taps is None else parse_taps(a.taps), noise=a.noise, generator=gen)
-        out = eng.receive_stream(samples, max_packets=a.max_packets, detector=a.detector, threshold=a.threshold)
+        out = eng.receive_stream(samples, max_packets=a.max_packets, detector=a.detector, threshold=a.threshold,
+                                 timing=a.timing)
     rec = out["records"]
+    timed = a.timing != "none"
     d = Path(a.out)
     d.mkdir(parents=True, exist_ok=True)
     with open(d / "packets.csv", "w", newline="") as f:
         wr = csv.writer(f)
-        wr.writerow(["packet_pos", "flags", "cfo_coarse_hz", "cfo_fine_hz", "bit_err", "evm_db_pre", "message"])
+        wr.writerow(["packet_pos", "flags", "cfo_coarse_hz", "cfo_fine_hz", "bit_err", "evm_db_pre", "message"]
+                    + (["coarse_pos"] if timed else []))
         for k in range(out["count"]):
             r = rec[k]
             row = [int(r["packet_pos"]), int(r["flags"]), float(r["cfo_coarse_hz"]), float(r["cfo_fine_hz"]),
                    int(r["bit_err"]), float(r["evm_db_pre"]), out["messages"][k]]
-            wr.writerow(row)
+            wr.writerow(row + ([int(out["coarse_pos"][k])] if timed else []))
             tags = "".join(t for bit, t in ((abi.CAPTURE_OOB, " oob"), (abi.STREAM_LAST_FRONT, " last-front")) if row[1] & bit)
             print(f"{row[0]:>12d}  flags {row[1]}{tags:<15s} cfo {row[2] + row[3]:+10.1f} Hz  bit_err {row[4]:4d}  {row[6]!r}")
     print(f"{out['found']} packets found, {out['count']} decoded of {len(samples)} samples -> {d / 'packets.csv'}",
@@ -280,5 +345,6 @@ def main(argv=None) -> int:
     return 0
 
 
-__all__ = ["select_packets", "detection_metric", "positions", "DETECTORS", "unpack_cross", "first_packet", "synthetic_segments", "main", "pack_messages",
+__all__ = ["ltf_template", "refine_timing", "TIMINGS", "LTF_START", "TIMING_BACK", "TIMING_FWD", "TIMING_CANDIDATES", "TIMING_FIRST", "TIMING_SPAN",
+           "select_packets", "detection_metric", "positions", "DETECTORS", "unpack_cross", "first_packet", "synthetic_segments", "main", "pack_messages",
            "transmit_main", "score_packets", "SCORE_MAX_WINDOW", "NSCORE", "MAX_DATA_SYMBOLS", "THRESHOLD", "FRONT_GAP", "CONFIRM", "PACKET_OFFSET", "LAST_FRONT"]

@@ -175,7 +175,7 @@ def captures_main(argv=None):
 
 def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: float = 0.0, taps=None,
                noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=None, fading=None,
-               detector: str = "reference", threshold: float = 0.75) -> dict:
+               detector: str = "reference", threshold: float = 0.75, timing: str = "none") -> dict:
     """Packet-error and bit-error counts against SNR for packets that each carry their own bits, the recording never
     leaving the device: the packets (words: uint32 [n, 3 n_data], each behind `gap` idle samples, and a closing gap)
     are transmitted once; per SNR point q the clean recording is impaired into a second buffer with the noise stream
@@ -193,11 +193,14 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     detector, threshold: Engine.receive_stream_device's (include/ofdm_mi355x_detect.h).  The default window is the same
     for both detectors: the conjugate detector's fronts are the reference's on an unfaded link, and under a selective
     channel at low SNR a few of its detections can fall outside it and count as missed.
+    timing: "none", or "ltf": every record's position is refined against the long training field before the decode
+    (include/ofdm_mi355x_timing.h), which puts an unfaded packet's record at its first sample + 16.
 
     Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
     import torch  # noqa: PLC0415
     snr = np.atleast_1d(np.asarray(snr_db, np.float64))
     n, plen = int(len(words)), abi.packet_len(n_data)
+    abi.timing_code(timing)                                          # ValueError before anything is set or launched
     pdp = None
     if fading is not None:
         if set(fading) - {"pdp", "index0"} or "pdp" not in fading:
@@ -230,7 +233,7 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     for q, s in enumerate(snr):
         engine.impair_stream(clean, power, float(s), cfo_hz, taps=taps, noise=noise, seed=seed, trial=trial,
                              snr_index=q, out=rec)
-        rx = engine.receive_stream_device(rec, detector=detector, threshold=threshold)
+        rx = engine.receive_stream_device(rec, detector=detector, threshold=threshold, timing=timing)
         engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])
     return dict(snr_db=snr, totals=totals.cpu().numpy(), power=power, packets=n, samples=n_out)
 
@@ -274,6 +277,8 @@ def link_main(argv=None) -> int:
     ap.add_argument("--detector", choices=tuple(abi.DETECTOR), default="reference",
                     help="the detection metric: the reference's, or delay-and-correlate with the conjugate at lag 32")
     ap.add_argument("--threshold", type=float, default=abi.DETECT_THRESHOLD, help="a crossing is M > threshold, inside (0, 1)")
+    ap.add_argument("--timing", choices=tuple(abi.TIMING), default="none",
+                    help="ltf: refine every packet's position against the long training field before the decode")
     ap.add_argument("--out", default="data")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:
@@ -299,7 +304,8 @@ def link_main(argv=None) -> int:
     t0 = time.perf_counter()
     with Engine(0) as eng:
         res = link_sweep(eng, words, d, a.gap, snr, cfo_hz=a.cfo_hz, taps=None if a.taps is None else parse_taps(a.taps),
-                         noise=a.noise, seed=a.seed, fading=fading, detector=a.detector, threshold=a.threshold)
+                         noise=a.noise, seed=a.seed, fading=fading, detector=a.detector, threshold=a.threshold,
+                         timing=a.timing)
     wall = time.perf_counter() - t0
     t = res["totals"]
     ber = t[:, abi.S_BIT_ERR] / np.maximum(t[:, abi.S_BITS], 1)
