@@ -161,7 +161,7 @@ _TIMING_SIGS = {
                                             _V, _V]),
 }
 TIMING_EXPORTS = tuple(_TIMING_SIGS)
-TIMING = {"none": 0, "ltf": 1}                   # OFDM_TIMING_NONE, OFDM_TIMING_LTF
+TIMING = {"none": 0, "ltf": 1, "ltf-matlab": 2}  # OFDM_TIMING_NONE, OFDM_TIMING_LTF, OFDM_TIMING_LTF_MATLAB
 TIMING_BACK, TIMING_FWD = 56, 8                  # OFDM_TIMING_BACK, OFDM_TIMING_FWD: shifts -56 .. +7
 
 
@@ -259,7 +259,7 @@ def stream_timing_dtype():
 
 
 def timing_code(timing: str) -> int:
-    """OFDM_TIMING_* of "none" or "ltf"; ValueError for anything else"""
+    """OFDM_TIMING_* of "none", "ltf" or "ltf-matlab"; ValueError for anything else"""
     if not isinstance(timing, str) or timing not in TIMING:
         raise ValueError(f"timing must be one of {tuple(TIMING)}, got {timing!r}")
     return TIMING[timing]

@@ -69,9 +69,10 @@ struct Ctx {
     int wave_frames = 0;
     int32_t wave_len = 0;
     double wave_power = 0.0;
-    // the fine timing template (ofdm_stream_timing.hip): w[394 .. 522) of Transmitter()'s waveform, built on first use
-    bool ltf_ready = false;
-    float2 ltf_template[128] = {};
+    // the fine timing templates (ofdm_stream_timing.hip): w[394 .. 522) of Transmitter()'s waveform under
+    // OFDM_CONV_C [0] and OFDM_CONV_MATLAB [1], each built on its first use
+    bool ltf_ready[2] = {false, false};
+    float2 ltf_template[2][128] = {};
     // kernel timing
     struct Ev { hipEvent_t a, b; int kernel; };
     bool timing = false;

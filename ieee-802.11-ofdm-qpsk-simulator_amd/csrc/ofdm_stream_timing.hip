@@ -22,6 +22,7 @@
 namespace ofdm {
 
 constexpr int TM_WAVES = 4;                                   // packets per block and sweep
+constexpr int TM_BLOCKS_PER_CU = 8;                           // the grid's cap: the waves loop past it
 constexpr int TM_CAND = OFDM_TIMING_BACK + OFDM_TIMING_FWD;   // 64: one candidate per lane
 constexpr int TM_LTF = 394;                                   // 2 * 192 + 10: the first long training symbol in the waveform
 constexpr int TM_FIRST = TM_LTF - 16 - OFDM_TIMING_BACK;      // 322: candidate 0 reads from p + 322
@@ -137,20 +138,24 @@ __global__ __launch_bounds__(64 * TM_WAVES) void stream_timing_kernel(TimArgs a)
     }
 }
 
-// w[394 .. 522) of the context's own Transmitter() waveform (frame_wave_kernel through ofdm_transmitter), once
+// w[394 .. 522) of the context's own Transmitter() waveform (frame_wave_kernel through ofdm_transmitter) under the
+// convention CONV, once per context and convention: the two templates are cached side by side
+template <int CONV>
 static int timing_prepare(const StreamRefiner *, Ctx *c) {
-    if (c->ltf_ready) return OFDM_OK;
+    static_assert(CONV == OFDM_CONV_C || CONV == OFDM_CONV_MATLAB, "one cached template per convention");
+    if (c->ltf_ready[CONV]) return OFDM_OK;
     std::vector<float2> w(10 * (2 * (320 + 80 * LONG_MAX_FRAMES) + 20));
     int32_t len = 0;
-    int rc = ofdm_transmitter(reinterpret_cast<ofdm_ctx *>(c), OFDM_CONV_C, OFDM_PAYLOAD_MESSAGE, 1,
+    int rc = ofdm_transmitter(reinterpret_cast<ofdm_ctx *>(c), CONV, OFDM_PAYLOAD_MESSAGE, 1,
                               reinterpret_cast<float *>(w.data()), (int32_t)w.size(), &len);
     if (rc) return rc;
     if (len < TM_LTF + TM_PERIOD) return set_error(OFDM_E_HIP, "Transmitter() gave %d samples, the template needs %d", len, TM_LTF + TM_PERIOD);
-    std::copy(w.begin() + TM_LTF, w.begin() + TM_LTF + TM_PERIOD, c->ltf_template);
-    c->ltf_ready = true;
+    std::copy(w.begin() + TM_LTF, w.begin() + TM_LTF + TM_PERIOD, c->ltf_template[CONV]);
+    c->ltf_ready[CONV] = true;
     return OFDM_OK;
 }
 
+template <int CONV>
 static void timing_launch(const StreamRefiner *ref, Ctx *c, hipStream_t stream, const RefineArgs &r) {
     TimArgs a{};
     a.x = r.x;
@@ -158,7 +163,7 @@ static void timing_launch(const StreamRefiner *ref, Ctx *c, hipStream_t stream, 
     a.count = r.count;
     a.pk = r.pk;
     a.out = (ofdm_stream_timing *)ref->out;
-    std::copy(c->ltf_template, c->ltf_template + TM_PERIOD, a.t);
+    std::copy(c->ltf_template[CONV], c->ltf_template[CONV] + TM_PERIOD, a.t);
     for (int s = 0; s < TM_NSEG; ++s) {
         double e = 0.0;
         for (int k = 0; k < TM_SEG; ++k) {
@@ -167,9 +172,9 @@ static void timing_launch(const StreamRefiner *ref, Ctx *c, hipStream_t stream, 
         }
         a.te[s] = (float)e;
     }
-    // the packet count stays on the device: enough blocks for max_packets, at most eight per CU; the waves loop
+    // the packet count stays on the device: enough blocks for max_packets, at most TM_BLOCKS_PER_CU per CU; the waves loop
     const int64_t blocks = (r.max_packets + TM_WAVES - 1) / TM_WAVES;
-    const dim3 grid((unsigned)std::min<int64_t>(blocks, 8 * (int64_t)c->cus));
+    const dim3 grid((unsigned)std::min<int64_t>(blocks, TM_BLOCKS_PER_CU * (int64_t)c->cus));
     hipLaunchKernelGGL(stream_timing_kernel, grid, dim3(64 * TM_WAVES), 0, stream, a);
 }
 
@@ -181,10 +186,10 @@ extern "C" int ofdm_receive_stream_timed(ofdm_ctx *ctx, const void *d_samples, i
                                          const ofdm_stream_opts *sopts, int timing, int payload, int64_t max_packets,
                                          void *d_packets, void *d_count, void *d_bits, void *d_eq, void *d_counters,
                                          void *d_metric, void *d_cross, void *d_timing) {
-    if (timing != OFDM_TIMING_NONE && timing != OFDM_TIMING_LTF)
-        return set_error(OFDM_E_ARG, "timing must be OFDM_TIMING_NONE (0) or OFDM_TIMING_LTF (1), got %d", timing);
+    if (timing != OFDM_TIMING_NONE && timing != OFDM_TIMING_LTF && timing != OFDM_TIMING_LTF_MATLAB)
+        return set_error(OFDM_E_ARG, "timing must be OFDM_TIMING_NONE (0), OFDM_TIMING_LTF (1) or OFDM_TIMING_LTF_MATLAB (2), got %d", timing);
     if (timing == OFDM_TIMING_NONE && d_timing)
-        return set_error(OFDM_E_ARG, "d_timing needs OFDM_TIMING_LTF: timing is OFDM_TIMING_NONE");
+        return set_error(OFDM_E_ARG, "d_timing needs OFDM_TIMING_LTF or OFDM_TIMING_LTF_MATLAB: timing is OFDM_TIMING_NONE");
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     // no timing is ofdm_receive_stream_ex itself: the same launches, byte-identical outputs
     if (timing == OFDM_TIMING_NONE)
@@ -192,8 +197,10 @@ extern "C" int ofdm_receive_stream_timed(ofdm_ctx *ctx, const void *d_samples, i
                                  d_counters, d_metric, d_cross, nullptr);
     StreamRefiner ref{};
     ref.kernel = OFDM_K_STREAM_TIMING;
-    ref.prepare = timing_prepare;
-    ref.launch = timing_launch;
+    // the same kernel under the same id; the recording's convention only chooses the template
+    const bool matlab = timing == OFDM_TIMING_LTF_MATLAB;
+    ref.prepare = matlab ? timing_prepare<OFDM_CONV_MATLAB> : timing_prepare<OFDM_CONV_C>;
+    ref.launch = matlab ? timing_launch<OFDM_CONV_MATLAB> : timing_launch<OFDM_CONV_C>;
     ref.name = "stream_timing_kernel";
     ref.out = d_timing;
     return stream_receive_ex(c, d_samples, n_samples, opts, sopts, payload, max_packets, d_packets, d_count, d_bits, d_eq,

@@ -474,7 +474,9 @@ class Engine:
         above over Lc = n - 47 positions, or "conjugate", the lag-32 delay-and-correlate metric with the conjugate over
         Lc = n - 63; a crossing is M > threshold, 0 < threshold < 1.  The defaults are ofdm_receive_stream itself.
         timing: "none", or "ltf" (ofdm_receive_stream_timed, include/ofdm_mi355x_timing.h): every packet_pos is refined
-        against the long training field before the decode (stream.refine_timing is the rule); the result then also
+        against the long training field before the decode (stream.refine_timing is the rule); "ltf-matlab" is the same
+        with the template of a MATLAB-convention waveform, for recordings made with conv="matlab" -- the recording's
+        convention decides, not mode=, which decodes either.  The result then also
         holds coarse_pos (int64 [count], front + 11), shift (int32, packet_pos - coarse_pos) and quality (float32,
         in [0, 1], 0 for a packet that was not refined) -- all three None with "none".
 
@@ -558,7 +560,7 @@ class Engine:
         one-dimensional contiguous torch complex64 tensor on this engine's device.  Returns d_packets (uint8
         [rows, 64], ofdm_stream_packet), d_count (int64 [2]: found, written) and d_words (int32 [rows, 3 D]), of which
         the first d_count[1] rows are written, and frames -- what score_packets takes.  detector, threshold: as
-        receive_stream's.  timing: as receive_stream's; d_timing (uint8 [rows, 16], ofdm_stream_timing) with "ltf", else
+        receive_stream's.  timing: as receive_stream's; d_timing (uint8 [rows, 16], ofdm_stream_timing) with "ltf" or "ltf-matlab", else
         None."""
         torch = _torch()
         opts = make_rx_opts(mode)

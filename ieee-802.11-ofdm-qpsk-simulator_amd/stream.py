@@ -100,7 +100,7 @@ def select_packets(cross_or_metric, thr: float = THRESHOLD) -> dict:
     return dict(fronts=fronts, confirmed=conf, positions=pos.astype(np.int64), flags=flags)
 
 
-TIMINGS = ("none", "ltf")
+TIMINGS = ("none", "ltf", "ltf-matlab")      # "ltf-matlab": the template of a MATLAB-convention waveform
 LTF_START = 394           # 2 * 192 + 10: the first long training symbol in one period of Transmitter()'s waveform
 TIMING_BACK = 56          # OFDM_TIMING_BACK: candidate j is the shift j - 56
 TIMING_FWD = 8            # OFDM_TIMING_FWD
@@ -113,7 +113,10 @@ TIMING_SEGMENT = 32       # the non-coherent segments: the short training field'
 def ltf_template(wave) -> np.ndarray:
     """The 256-sample template of the fine timing rule (include/ofdm_mi355x_timing.h) from one period of
     Transmitter()'s 40 MS/s waveform: t[k] = wave[394 + (k mod 128)], the first long training symbol, which is cyclic
-    on both sides and does not depend on the payload or on the number of data symbols.  complex128 [256]."""
+    on both sides and does not depend on the payload or on the number of data symbols.  complex128 [256].
+    It does depend on the transform convention of the waveform: ltf_template(w_c) is the template of OFDM_TIMING_LTF
+    ("ltf"), ltf_template(w_matlab) that of OFDM_TIMING_LTF_MATLAB ("ltf-matlab") and its specification; the second is
+    the first rotated by half a period, np.roll(t_c, -64), exactly."""
     w = np.asarray(wave).astype(np.complex128).reshape(-1)
     if len(w) < LTF_START + 128:
         raise ValueError(f"a waveform of at least {LTF_START + 128} samples expected, got {len(w)}")
@@ -130,7 +133,10 @@ def refine_timing(x, positions, template) -> dict:
     [0, 1] and invariant to the scale of x and of t.
 
     Returns positions (int64, refined), coarse (int64), shift (int32), quality (float64) and metric (float64
-    [n, 64], L; zeros for a packet that was not refined)."""
+    [n, 64], L; zeros for a packet that was not refined).
+    The rule takes any template: with ltf_template of a C-convention waveform it specifies OFDM_TIMING_LTF, with that
+    of a MATLAB-convention waveform OFDM_TIMING_LTF_MATLAB.  The template has to be of the recording's convention:
+    the other one moves every packet 4 samples late at a quality near 0.3, and at large carrier offsets further."""
     x = np.asarray(x).astype(np.complex128).reshape(-1)
     t = np.asarray(template).astype(np.complex128).reshape(-1)
     if len(t) != 256:
@@ -301,7 +307,8 @@ def main(argv=None) -> int:
     ap.add_argument("--threshold", type=float, default=THRESHOLD, help="a crossing is M > threshold, inside (0, 1)")
     ap.add_argument("--timing", choices=TIMINGS, default="none",
                     help="ltf: refine every packet's position against the long training field before the decode "
-                         "(packets.csv then has a coarse_pos column)")
+                         "(packets.csv then has a coarse_pos column); ltf-matlab: the same for a recording made "
+                         "with the MATLAB transform convention")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:
         raise SystemExit("--threshold must be inside (0, 1)")

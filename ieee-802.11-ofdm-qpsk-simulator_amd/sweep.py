@@ -194,7 +194,9 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     for both detectors: the conjugate detector's fronts are the reference's on an unfaded link, and under a selective
     channel at low SNR a few of its detections can fall outside it and count as missed.
     timing: "none", or "ltf": every record's position is refined against the long training field before the decode
-    (include/ofdm_mi355x_timing.h), which puts an unfaded packet's record at its first sample + 16.
+    (include/ofdm_mi355x_timing.h), which puts an unfaded packet's record at its first sample + 16.  "ltf-matlab" is accepted as well and is the same
+    rule with the MATLAB convention's template; the sweep transmits C-convention packets, for which "ltf" is the
+    right one.
 
     Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
     import torch  # noqa: PLC0415
@@ -278,7 +280,8 @@ def link_main(argv=None) -> int:
                     help="the detection metric: the reference's, or delay-and-correlate with the conjugate at lag 32")
     ap.add_argument("--threshold", type=float, default=abi.DETECT_THRESHOLD, help="a crossing is M > threshold, inside (0, 1)")
     ap.add_argument("--timing", choices=tuple(abi.TIMING), default="none",
-                    help="ltf: refine every packet's position against the long training field before the decode")
+                    help="ltf: refine every packet's position against the long training field before the decode "
+                         "(ltf-matlab: with the MATLAB convention's template)")
     ap.add_argument("--out", default="data")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:

@@ -30,6 +30,26 @@
  *              rule), max_packets, d_count, ofdm_stream_packet.reserved = 0 and the whole decode chain, which runs at
  *              the refined position: packet_idx is the refined position.
  *
+ * The recording's transform convention chooses the template, and the caller has to say which: ofdm_rx_opts carries no
+ * convention (mode "c" decodes recordings of either one).  OFDM_TIMING_LTF takes w from Transmitter() under
+ * OFDM_CONV_C and is for C-convention recordings.  OFDM_TIMING_LTF_MATLAB is the same rule word for word with w from
+ * Transmitter() under OFDM_CONV_MATLAB, for recordings of that convention (ofdm_transmit_packets with
+ * OFDM_CONV_MATLAB, the MATLAB tester's waveform).  The two long training symbols are each other's rotation by half
+ * a period, w_matlab[394 + k] == w_c[394 + ((k + 64) mod 128)] exactly; the short training field and everything
+ * before sample 320 are the same to rounding, so detection does not see the convention.  The wrong template still finds a peak,
+ * a weak one in the wrong place.  stream.refine_timing in fp64 on MATLAB-convention streams of the oracle's
+ * Transmitter(), C template against MATLAB template:
+ *   noise-free, 0 Hz, 2 or 15 data symbols   every packet at first sample + 20 (coarse: + 16), quality 0.27 .. 0.30,
+ *                                            against + 16 and 0.986 .. 1.000
+ *   noise-free, +200 kHz                     positions - 38 .. + 20, 339 bit errors of 18 packets (2 symbols) and
+ *                                            1,193 of 7 (15 symbols) where the coarse positions give 0, against + 16,
+ *                                            quality 0.90 .. 0.91 and 0 errors
+ *   14 and 25 dB, +-40 / -90 kHz             + 20 always -- the decode's 4 samples of margin all spent -- quality
+ *                                            0.26 .. 0.30, against + 16 always and 0.93 .. 0.99
+ * On an MI355X OFDM_TIMING_LTF_MATLAB gives the fp64 rule's position on all 84 packets of six such noisy and faded
+ * streams (quality within 2.9e-7 of fp64) and decodes the noise-free 200 kHz streams at + 16 without a bit error, where
+ * OFDM_TIMING_LTF makes 51 (2 symbols) and 394 (15 symbols).
+ *
  * The base header's function list, OFDM_ABI_VERSION, ofdm_mi355x_stream.h and ofdm_mi355x_detect.h are unchanged; a
  * caller that never includes this file sees the library exactly as before.
  */
@@ -42,7 +62,8 @@ extern "C" {
 #endif
 
 #define OFDM_TIMING_NONE 0            /* packet_pos = front + 11, as ofdm_receive_stream_ex */
-#define OFDM_TIMING_LTF 1             /* refined against the long training field */
+#define OFDM_TIMING_LTF 1             /* refined against the long training field of a C-convention recording */
+#define OFDM_TIMING_LTF_MATLAB 2      /* the same rule, template of OFDM_CONV_MATLAB: for MATLAB-convention recordings */
 #define OFDM_TIMING_BACK 56           /* the search reaches this many samples back from the coarse position ... */
 #define OFDM_TIMING_FWD 8             /* ... and up to this many forward, exclusive: shifts -56 .. +7 */
 
@@ -59,10 +80,13 @@ typedef struct {                 /* 16 bytes, one per record */
  * timing   OFDM_TIMING_NONE: the call is ofdm_receive_stream_ex itself, the same launches and byte-identical
  *          outputs; d_timing must then be NULL.  OFDM_TIMING_LTF: one more launch between the selection and the
  *          decode, under the timing id OFDM_K_STREAM_TIMING, rewrites packet_pos of the first d_count[1] records
- *          by the rule above.
- * d_timing optional, ofdm_stream_timing [max_packets] on the device; the first d_count[1] rows are written.
- * The call does not synchronise and allocates nothing, except that the first OFDM_TIMING_LTF call of a context builds
- * the template (Transmitter() once, and a wait for it).
+ *          by the rule above.  OFDM_TIMING_LTF_MATLAB: the same kernel launched under the same id with the
+ *          MATLAB convention's template.
+ * d_timing optional, ofdm_stream_timing [max_packets] on the device; the first d_count[1] rows are written.  Allowed
+ *          with OFDM_TIMING_LTF and OFDM_TIMING_LTF_MATLAB.
+ * The call does not synchronise and allocates nothing, except that a context's first call with OFDM_TIMING_LTF and
+ * its first with OFDM_TIMING_LTF_MATLAB each build their template (Transmitter() once, and a wait for it); the context
+ * keeps both, and neither disturbs the other.
  * OFDM_E_ARG, with an ofdm_last_error text and before any launch: an unknown timing; d_timing with OFDM_TIMING_NONE;
  * and everything ofdm_receive_stream_ex refuses. */
 int ofdm_receive_stream_timed(ofdm_ctx *ctx, const void *d_samples, int64_t n_samples,

@@ -111,6 +111,43 @@ def test_gpu_streams_have_no_decision_on_the_threshold(pkg, oracle):
         assert found == len(pos) or (faded and found >= 0.75 * len(pos)) or (snr == 14 and found >= len(pos) - 1)
 
 
+# the largest share of positions inside the band on the six streams, either detector: 3.315e-4 (D = 2, 14 dB, -90 kHz,
+# faded, the reference's metric), which is 3.3e-4 to the two figures it is stated with
+MATLAB_BAND_SHARE = 3.3e-4
+
+
+def test_matlab_streams_have_no_decision_on_the_threshold(pkg, oracle):
+    """the conditions on the MATLAB-convention streams of tests/test_gpu_matlab_stream.py (detect_ref.MATLAB_SEEDS) that
+    concern detection: no decision of either detector in the band, the band's share, what each detector finds.  A
+    change of the generators fails here and not on the GPU."""
+    from ofdm_amd.stream import detection_metric, select_packets
+    assert len(ref.MATLAB_SEEDS) == 6 and set(ref.MATLAB_SEEDS) == set(ref.MATLAB_FOUND)
+    for key, seed in ref.MATLAB_SEEDS.items():
+        d, snr, cfo, faded = key
+        assert seed % 1000 == (12000 + 100 * d + 10 * snr + faded) % 1000 and seed >= 12000       # the scheme
+        x, pos = ref.matlab_stream(oracle, key)
+        assert x.dtype == np.complex64 and 2e4 <= len(x) <= 5e4 and len(x) > 3 * pkg.abi.STREAM_TILE
+        found = {}
+        for det in ("reference", "conjugate"):
+            m = detection_metric(x, det)
+            share = len(ref.band_positions(m, 0.75, 0.75e-3)) / len(m)
+            found[det] = len(select_packets(m)["positions"])
+            print(f"matlab {key} seed {seed} {det}: {found[det]} of {len(pos)} packets, band share {share:.3g}")
+            assert ref.band_is_harmless(m, 0.75, 0.75e-3), (key, det)
+            assert round(share, 5) <= MATLAB_BAND_SHARE <= 0.01, (key, det)
+        assert (found["conjugate"], len(pos)) == ref.MATLAB_FOUND[key]
+        if cfo == 200e3:
+            assert found["reference"] == 0
+        elif faded:
+            assert 4 <= found["reference"] <= 5
+    # the default argument is the stream the builders made before they took one
+    key = (2, 14, 40e3, False)
+    a = ref.noisy_stream(oracle, *key, ref.STREAM_SEEDS[key])
+    b = ref.noisy_stream(oracle, *key, ref.STREAM_SEEDS[key], conv="c")
+    assert a[0].tobytes() == b[0].tobytes() and np.array_equal(a[1], b[1])
+    assert a[0].tobytes() != ref.noisy_stream(oracle, *key, ref.STREAM_SEEDS[key], conv="matlab")[0].tobytes()
+
+
 # ---------------------------------------------------------------- the header, the binding, the build
 def test_detect_header_is_exported_and_bound(pkg):
     abi = pkg.abi

@@ -50,7 +50,23 @@ A and B together under 10 ms; the receive_stream fixtures 0.17 s (A clean), 0.09
 the selection tests that first use them; the first transmitter case 0.29 s, the other ten under 5 ms each; the sentinel
 test 0.14 s; LAST_FRONT 0.09 s; max_packets 0.01 s; detection under 5 ms each; decode clean under 5 ms each, impaired
 0.14 s (A) and 0.02 s (B); channel 0.02 and 0.04 s; scoring under 5 ms, 0.13 s and 0.08 s.  The whole `-m gpu` suite: 62 s
-with this module."""
+with this module.
+
+Section 7, the optional kernels (ofdm_receive_stream_ex's detectors, ofdm_receive_stream_timed's kernel, scoring of
+refined positions), measured on an MI355X (256 CUs, 2026-10-20).  B through the conjugate detector: Lc = n - 63 =
+78,995,628 positions in 9,955 tiles and 1,026 selection blocks (two trips of phase 1); 31,681 of 31,749 packets found at
+14 dB, all 31,749 at offset 16 noise-free; on the six ranges no crossing differs off the band (at most 3 positions of a
+range in it), metric within 1.25e-6 of fp64 (4 x CONJ_DEV_MEASURED 1.44e-5).  Threshold 0.6 on the reference's metric:
+31,731 found, no crossing differs off a band of 6e-4, a superset of the default call's crossings.  Timing on B: 31,681
+records on 2,048 blocks of 4 waves, 3.87 trips of 8,192 (7,105 records in the last); 26,423 records moved, shifts -56 to
++7; all 31,643 records within a packet's first 100 samples at offset 16; 10,156 records against fp64: shift exact,
+quality within 4.5e-7 (4 x TIMING_DEV_MEASURED 1.32e-6), smallest gap between the two largest L 0.041.  Timing on A
+(reference detector, 4,099 records: the conjugate one finds 4,090 there, under the decode's wrap at 4,096): half a trip
+of the timing grid on 256 CUs, 3,580 records moved, every record at offset 16, 200 records within 3.3e-7 of fp64.  64
+moved records of each against the oracle's decode at the refined position: CFO within 0.0044 Hz.  Scoring B's refined positions: 31,643 matched with (16, 16), (8, 40) and (0, 300) alike, 0 bit errors
+against 69 at the coarse positions; neighbouring records at least 603 apart.  Wall time: the four detector cases 0.09 to
+0.14 s each; the timed fixture (four receive_stream runs) 0.42 s; the timing test 0.38 s, its launch shapes 0.08 s; the
+others 0.02 s or less.  The whole `-m gpu` suite: 65 s with this section and tests/test_gpu_matlab_stream.py."""
 import math
 import time
 
@@ -58,11 +74,14 @@ import numpy as np
 import pytest
 
 import channel_ref as cref
+import timing_ref as tr
 from conftest import normwise
 from fading_ref import rand_taps
-from test_gpu_captures import CFO_TOL_HZ, check_against_receiver
+from test_gpu_captures import CFO_TOL_HZ, check_against_oracle, check_against_receiver
+from test_gpu_detect import BAND_REL, CONJ_DEV_MEASURED, METRIC_FLOOR
 from test_gpu_stream import BAND, assert_selection_exact, metric64
-from test_gpu_transmit import rand_words, same_bits
+from test_gpu_timing import TIMING_DEV_MEASURED
+from test_gpu_transmit import bits_of, rand_words, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -79,12 +98,15 @@ CH_THREADS = 256             # csrc/ofdm_channel.hip:32
 CH_QUAD = 4                  # csrc/ofdm_channel.hip:33  CH_TILE = 4 * CH_THREADS: samples per channel quad
 CH_MAX_GRID = 2048           # csrc/ofdm_channel.hip:34
 SC_THREADS = 256             # csrc/ofdm_channel.hip:156 transmitted packets per score block
+TM_WAVES = 4                 # csrc/ofdm_stream_timing.hip:24 packets per block and sweep of the timing kernel
+TM_BLOCKS_PER_CU = 8         # csrc/ofdm_stream_timing.hip:25 its grid's cap
 MIRRORED = {
     "ofdm_stream.hip": dict(SS_THREADS=SS_THREADS, SS_SLOT=SS_SLOT, SS_SCAN_THREADS=SS_SCAN_THREADS,
                             SDEC_MAX_WAVES=SDEC_MAX_WAVES),
     "ofdm_transmit.hip": dict(TXP_GROUP_SYMS=TXP_GROUP_SYMS, TXP_BLOCKS_PER_CU=TXP_BLOCKS_PER_CU),
     "ofdm_fading.hip": dict(FD_GROUP_SYMS=FD_GROUP_SYMS, FD_BLOCKS_PER_CU=FD_BLOCKS_PER_CU),
     "ofdm_channel.hip": dict(CH_THREADS=CH_THREADS, CH_MAX_GRID=CH_MAX_GRID, SC_THREADS=SC_THREADS),
+    "ofdm_stream_timing.hip": dict(TM_WAVES=TM_WAVES, TM_BLOCKS_PER_CU=TM_BLOCKS_PER_CU),
 }
 CH_TILE = CH_QUAD * CH_THREADS
 DETECT_TILE = 7936           # abi.STREAM_TILE, asserted in the detection test
@@ -662,3 +684,314 @@ def test_scoring_with_records_cut_inside_a_score_block(eng, pkg, rx, recs):
     print(f"score B with {m} records: the last matched packet is {last} (block {last // SC_THREADS}, thread {last % SC_THREADS})")
     assert last % SC_THREADS not in (0, SC_THREADS - 1) and (scores[last + 1:, 0] == -1).all()
     assert np.array_equal(scores[:last + 1], _score_both(eng, pkg, r, full)[0][:last + 1])
+
+
+# ------------------------------------------------------------------------------------------- 7. the optional kernels
+# ofdm_receive_stream_ex's detectors and ofdm_receive_stream_timed's kernel on the same recordings: tiles far from the
+# start, the selection and the decode with the conjugate detector's Lc = n - 63 where their loops carry, the timing
+# kernel's own packet loop (i += gridDim.x * TM_WAVES, the grid capped at TM_BLOCKS_PER_CU blocks per CU) past its
+# first trip, and ofdm_score_packets on refined positions.
+OPTIONAL_DETECTORS = [("conjugate", 0.75), ("reference", 0.6)]      # stream_detect_conj_kernel, stream_detect_thr_kernel
+
+
+def receive_opt(eng, r, x, detector="conjugate", threshold=0.75, timing="none", **kw):
+    """receive() with ofdm_receive_stream_ex's and ofdm_receive_stream_timed's options: the bitmap has the detector's
+    own Lc positions"""
+    from ofdm_amd.stream import positions, select_packets, unpack_cross
+    assert eng.set_long_message(TEXT[r["d"]]) == r["d"]
+    out = eng.receive_stream(x, detector=detector, threshold=threshold, timing=timing, **kw)
+    if out["cross"] is not None:
+        out["bitmap"] = unpack_cross(out["cross"].cpu().numpy(), positions(len(x), detector))
+        out["sel"] = select_packets(out["bitmap"])
+    return out
+
+
+@pytest.mark.parametrize("kind", ["noisy", "clean"])
+@pytest.mark.parametrize("detector,threshold", OPTIONAL_DETECTORS)
+def test_optional_detectors_at_scale(eng, pkg, rx, recs, detector, threshold, kind):
+    from ofdm_amd.stream import detection_metric, positions
+    T = pkg.abi.STREAM_TILE
+    r = recs["B"]
+    halo = r["n"] - positions(r["n"], detector)
+    lc = r["n"] - halo
+    tiles = -(-lc // T)
+    nslots = -(-lc // SS_SLOT)
+    nblocks = -(-nslots // SS_THREADS)
+    conj = detector == "conjugate"
+    t0 = time.perf_counter()
+    out = receive_opt(eng, r, r[kind], detector, threshold, want_bits=False, want_cross=True, want_metric=conj)
+    _torch().cuda.synchronize()
+    print(f"optional detector {detector} {threshold} B {kind}: Lc {lc} (halo {halo}), {tiles} tiles, {nslots} slots in {nblocks} "
+          f"selection blocks, phase 1 trips {-(-nblocks // SS_SCAN_THREADS)}; found {out['found']} of {r['n_tx']}, "
+          f"{time.perf_counter() - t0:.2f} s")
+    assert halo == (63 if conj else 47) and nblocks > SS_SCAN_THREADS and tiles > 9000
+    got_all = out["bitmap"]
+    rng = np.random.default_rng(0xDE7EC7)
+    starts = [0, (tiles - 2) * T] + [int(t) * T for t in rng.integers(1, tiles - 3, 2)] \
+        + [int(s) for s in rng.integers(T, lc - 3 * T, 2)]
+    assert lc % T != 0 and all(s % T == 0 for s in starts[:4]) and all(s % T for s in starts[4:])
+    worst = 0.0
+    for s in starts:
+        e = min(s + 2 * T, lc)
+        x = r[kind][s:e + halo].cpu().numpy()
+        ref = detection_metric(x, detector)
+        got = got_all[s:e]
+        ok = np.isfinite(ref)
+        with np.errstate(invalid="ignore"):
+            want = ref > threshold
+            band = np.abs(ref - threshold) <= BAND_REL * threshold
+        diff = int((got != want)[~band].sum())
+        text = ""
+        if conj:
+            g = out["metric"][s:e].cpu().numpy().astype(np.float64)
+            dev = float((np.abs(g[ok] - ref[ok]) / np.maximum(ref[ok], METRIC_FLOOR)).max())
+            worst = max(worst, dev)
+            text = f", metric deviation {dev:.3g} (4 x CONJ_DEV_MEASURED {4 * CONJ_DEV_MEASURED:.3g})"
+            assert np.isfinite(g[ok]).all()
+        print(f"detect {detector} {threshold} B {kind}: positions [{s}, {e}) (tiles {s // T} .. {(e - 1) // T} of {tiles}): "
+              f"{int(got.sum())} crossings, {diff} differ off the band, {int(band.sum())} positions ({100 * band.mean():.2f} %) in it, "
+              f"{int((got != want)[band].sum())} differ there{text}")
+        assert len(ref) == e - s and got.any()
+        assert diff == 0
+        assert band.mean() <= 0.01
+        assert not got[~ok].any()
+    if conj:
+        assert BAND_REL * 0.75 == BAND and 4 * CONJ_DEV_MEASURED < 1e-3 and worst <= 4 * CONJ_DEV_MEASURED
+    else:
+        # the two kernels' sums are bit-identical, so the default call's 0.75-crossings nest in the 0.6-crossings
+        base = rx("B", kind)["bitmap"]
+        assert len(base) == len(got_all) and not (base & ~got_all).any() and got_all.sum() > base.sum()
+    # the selection on the whole bitmap, with the detector's own Lc
+    assert len(got_all) == lc
+    assert_selection_exact(out)
+    assert out["found"] == out["count"] and int(out["positions"].max()) < 2 ** 31
+    last_conf = int(out["positions"][-1]) - 11
+    assert last_conf // SS_SLOT >= SS_THREADS * SS_SCAN_THREADS      # behind the carry of phase 1's outer loop
+    if kind == "clean" and conj:
+        # tests/test_scale_host.py: every payload row alone is found once at offset 16 by this detector too
+        assert out["found"] == r["n_tx"] and np.array_equal(out["positions"], r["pos"] + OFFSET)
+
+
+def test_max_packets_cuts_at_a_blocks_prefix_under_the_conjugate_detector(eng, timed, recs):
+    r = recs["B"]
+    full = timed["B"]["none"]
+    fronts = full["positions"] - 11
+    prefix = int((fronts < SS_SCAN_THREADS * SS_THREADS * SS_SLOT).sum())     # the first block of phase 1's second trip
+    assert 0 < prefix < full["found"]
+    o = receive_opt(eng, r, r["noisy"], max_packets=prefix, want_bits=False)
+    print(f"conjugate detector, max_packets {prefix}: found {o['found']}, count {o['count']}")
+    assert o["found"] == full["found"] and o["count"] == prefix == len(o["records"])
+    assert o["records"].tobytes() == full["records"][:prefix].tobytes()
+
+
+# ---- timing
+TIMED_DETECTOR = {"B": "conjugate", "A": "reference"}
+
+
+@pytest.fixture(scope="module")
+def tmpl(pkg, oracle):
+    return tr.template(oracle)
+
+
+@pytest.fixture(scope="module")
+def timed(eng, recs):
+    """name -> the noisy recording without timing and with "ltf", each with bits, eq, a counters row and the device
+    tensors; built once and left unchanged.  B through the conjugate detector.  A through the reference's: at 14 dB it
+    finds 4,099 of A's packets and the conjugate one 4,090, and A is here for the decode loop's wrap past
+    SDEC_MAX_WAVES * cap = 4,096 records."""
+    torch = _torch()
+    out = {}
+    for name in "BA":
+        r = recs[name]
+        out[name] = {}
+        for timing in ("none", "ltf"):
+            t0 = time.perf_counter()
+            row = eng.new_counters(1)[0]
+            o = receive_opt(eng, r, r["noisy"], TIMED_DETECTOR[name], timing=timing, want_bits=True, want_eq=True, counters=row,
+                            keep_device=True)
+            o["row"] = row.cpu().numpy().copy()
+            torch.cuda.synchronize()
+            print(f"receive_stream {name} noisy, {TIMED_DETECTOR[name]} detector, timing {timing}: found {o['found']}, count {o['count']}, "
+                  f"{time.perf_counter() - t0:.2f} s")
+            out[name][timing] = o
+    return out
+
+
+def _timing_trip(dev) -> int:
+    return TM_BLOCKS_PER_CU * dev["cus"] * TM_WAVES
+
+
+def _whole_run_assertions(r, none, ltf):
+    """what holds for every record of a timed run, whatever the recording"""
+    n, count = r["n"], ltf["count"]
+    assert count == ltf["found"] == none["count"] == none["found"]
+    assert np.array_equal(ltf["coarse_pos"], none["positions"])                       # byte-identical: both int64
+    assert ltf["coarse_pos"].tobytes() == none["positions"].tobytes()
+    assert np.array_equal(ltf["positions"], ltf["coarse_pos"] + ltf["shift"])
+    assert (np.diff(ltf["positions"]) > 0).all()                                      # "the records stay ascending"
+    assert ((ltf["shift"] >= -56) & (ltf["shift"] <= 7)).all()
+    inside = ltf["coarse_pos"] + tr.SPAN < n
+    q = ltf["quality"]
+    assert np.isfinite(q).all() and ((q[inside] > 0) & (q[inside] <= 1)).all()
+    assert not q[~inside].any() and not ltf["shift"][~inside].any()
+    rec = ltf["records"]
+    assert np.array_equal(rec["packet_pos"], ltf["positions"])
+    assert np.array_equal(rec["packet_idx"], rec["packet_pos"].astype(np.int32)) and not rec["reserved8"].any()
+    # a record that did not move is the untimed record, eq included
+    keep = np.nonzero(ltf["shift"] == 0)[0]
+    assert rec[keep].tobytes() == none["records"][keep].tobytes()
+    keep_dev = _torch().from_numpy(keep).cuda()
+    assert dev_same_bits(ltf["eq"][keep_dev], none["eq"][keep_dev])
+    return inside, keep
+
+
+def _subset_against_fp64(r, ltf, picks, tmpl):
+    """the records `picks`: their 641 samples [p, p + 641) from the device in one gather, stream.refine_timing on them
+    with the oracle's template; shift exactly and quality under test_gpu_timing's bound.  Returns the largest quality
+    deviation and the smallest relative gap between the two largest fp64 L."""
+    from ofdm_amd.stream import refine_timing
+    torch = _torch()
+    picks = np.asarray(picks)
+    coarse = ltf["coarse_pos"][picks]
+    assert (coarse >= 0).all() and (coarse + tr.SPAN < r["n"]).all()
+    at = torch.from_numpy(coarse).cuda()[:, None] + torch.arange(tr.SPAN + 1, device="cuda")[None, :]
+    y = r["noisy"][at].cpu().numpy().reshape(-1)
+    want = refine_timing(y, (tr.SPAN + 1) * np.arange(len(picks)), tmpl)
+    gap = float(tr.top_gap(want["metric"]).min())
+    dev = float(np.abs(ltf["quality"][picks].astype(np.float64) - want["quality"]).max())
+    print(f"timing {r['name']}: {len(picks)} records against fp64: smallest gap between the two largest L {gap:.3g}, shifts "
+          f"{int(want['shift'].min())}..{int(want['shift'].max())}, quality {want['quality'].min():.3f}..{want['quality'].max():.3f}, "
+          f"largest quality deviation {dev:.3g} (4 x TIMING_DEV_MEASURED {4 * TIMING_DEV_MEASURED:.3g})")
+    assert gap > 1.2e-4                                               # before equality is demanded
+    assert np.array_equal(ltf["shift"][picks], want["shift"])
+    assert 4 * TIMING_DEV_MEASURED < 6e-5 and dev <= 4 * TIMING_DEV_MEASURED
+    return dev, gap
+
+
+def test_timing_when_the_packet_loop_wraps(eng, pkg, dev, timed, recs, tmpl):
+    r = recs["B"]
+    none, ltf = timed["B"]["none"], timed["B"]["ltf"]
+    count, trip = ltf["count"], _timing_trip(dev)
+    full, ragged = count // trip, count % trip
+    print(f"timing B: {count} records on {TM_BLOCKS_PER_CU * dev['cus']} blocks of {TM_WAVES} waves: {count / trip:.2f} trips of "
+          f"{trip} ({full} full, {ragged} records in the last)")
+    assert count > trip and ragged != 0                              # more than one trip, the last one ragged
+    inside, keep = _whole_run_assertions(r, none, ltf)
+    assert inside.all()                                               # B ends in a closing gap of 1,000
+    print(f"timing B: shifts {int(ltf['shift'].min())}..{int(ltf['shift'].max())}, {count - len(keep)} records moved, quality "
+          f"{ltf['quality'].min():.3f}..{ltf['quality'].max():.3f}")
+    # every record that belongs to a transmitted packet sits at its first sample + 16
+    off, _ = tr.offsets(ltf["positions"], r["pos"])
+    real = (off >= 0) & (off < 100)
+    coff, _ = tr.offsets(none["positions"], r["pos"])
+    print(f"timing B: {int(real.sum())} records within a packet's first 100 samples, coarse offsets "
+          f"{int(coff[real].min())}..{int(coff[real].max())}, refined {sorted(set(off[real].tolist()))}")
+    assert real.sum() > 0.99 * count and (off[real] == OFFSET).all()
+    # the fp64 rule on the first records, the ragged trip and 1,000 seeded records of each full trip
+    rng = np.random.default_rng(0x71317)
+    picks = list(range(64)) + list(range(count - ragged, count))
+    for t in range(full):
+        picks += (t * trip + rng.choice(trip, 1000, replace=False)).tolist()
+    picks = np.unique(picks)
+    assert len(picks) >= 64 + ragged + 1000 * full - 64 and (picks // trip).max() == full
+    _subset_against_fp64(r, ltf, picks, tmpl)
+    # the counters row is the reduction of the records
+    assert np.array_equal(ltf["row"], pkg.abi.reduce_capture_records(ltf["records"], r["d"]))
+
+
+def test_timing_launch_shapes_at_the_wrap(eng, dev, timed, recs):
+    r = recs["B"]
+    full = timed["B"]["ltf"]
+    trip = _timing_trip(dev)
+    assert full["count"] > trip + 1
+    for m in (trip, trip + 1):                                        # one exact trip with no wrap; one record into the second
+        o = receive_opt(eng, r, r["noisy"], timing="ltf", max_packets=m, want_bits=True, want_eq=True, keep_device=True)
+        blocks = min(-(-m // TM_WAVES), TM_BLOCKS_PER_CU * dev["cus"])
+        print(f"timing B, max_packets {m}: {blocks} blocks, {-(-m // (blocks * TM_WAVES))} trips; found {o['found']}, count {o['count']}")
+        assert o["found"] == full["found"] and o["count"] == m
+        assert o["records"].tobytes() == full["records"][:m].tobytes()
+        assert o["d_timing"][:m].cpu().numpy().tobytes() == full["d_timing"][:m].cpu().numpy().tobytes()
+        assert bool(_torch().equal(o["d_words"][:m], full["d_words"][:m])) and dev_same_bits(o["eq"], full["eq"][:m])
+
+
+def test_timed_decode_at_the_moved_positions(eng, oracle, timed, recs):
+    """64 seeded records whose position the timing kernel moved, against the oracle's decode_at at the refined position
+    on the recording's own samples.  (Receiver()'s own Packet_Selection on a window cut at the refined position finds
+    its own coarse position, not the refined one, so receive_captures cannot stand in here as it does for the untimed
+    records of test_decode_when_the_loop_wraps_impaired; records that did not move are byte-identical to those.)"""
+    from ofdm_amd.stream import pack_messages
+    torch = _torch()
+    for name in "BA":
+        r = recs[name]
+        d = r["d"]
+        ltf = timed[name]["ltf"]
+        moved = np.nonzero(ltf["shift"])[0]
+        nfr = 320 + 80 * d
+        L = 2 * nfr + 100
+        ok = moved[(ltf["positions"][moved] - 40 >= 0) & (ltf["positions"][moved] - 40 + L <= r["n"])]
+        picks = np.sort(np.random.default_rng(0x5EED + d).choice(ok, 64, replace=False))
+        at = torch.from_numpy(ltf["positions"][picks] - 40).cuda()[:, None] + torch.arange(L, device="cuda")[None, :]
+        caps = r["noisy"][at].cpu().numpy().astype(np.complex128)
+        truth = bits_of(pack_messages([TEXT[d]], d)[0])[0]
+        ora = [oracle.decode_at(c, truth, 40, dumps=True, cap_len=L) for c in caps]
+        rec = ltf["records"][picks].copy()
+        rec["packet_idx"] = 40
+        rec["flags"] &= 3
+        picks_dev = torch.from_numpy(picks).cuda()
+        bits, eq = ltf["bits"][picks_dev].cpu().numpy(), ltf["eq"][picks_dev].cpu().numpy()
+        same = check_against_oracle(rec, bits, eq, ora, list(caps), truth, 0)
+        cfo_dev = max(max(abs(float(rec["cfo_coarse_hz"][k]) - float(ora[k]["cfo"][0])),
+                          abs(float(rec["cfo_fine_hz"][k]) - float(ora[k]["cfo"][1]))) for k in same)
+        print(f"timed decode {name}: {len(moved)} records moved (shifts {sorted(set(ltf['shift'][picks].tolist()))} among the 64 picked), "
+              f"CFO estimates within {cfo_dev:.4g} Hz of the oracle's")
+        assert len(same) == 64 and cfo_dev <= CFO_TOL_HZ
+
+
+def test_timing_on_fifteen_symbol_packets_at_the_decode_wrap(eng, pkg, dev, timed, recs, tmpl):
+    r = recs["A"]
+    none, ltf = timed["A"]["none"], timed["A"]["ltf"]
+    count, trip = ltf["count"], _timing_trip(dev)
+    print(f"timing A: {count} records, {count / trip:.2f} trips of the timing grid ({trip}): "
+          f"{'wraps' if count > trip else 'does not wrap on this device'}; the decode loop wraps past {SDEC_MAX_WAVES * dev['cap']}")
+    assert count > SDEC_MAX_WAVES * dev["cap"]
+    inside, keep = _whole_run_assertions(r, none, ltf)
+    off, _ = tr.offsets(ltf["positions"], r["pos"])
+    real = (off >= 0) & (off < 100)
+    print(f"timing A: {count - len(keep)} records moved, refined offsets {sorted(set(off[real].tolist()))}, quality "
+          f"{ltf['quality'][inside].min():.3f}..{ltf['quality'].max():.3f}")
+    assert real.sum() > 0.99 * count and (off[real] == OFFSET).all()
+    picks = np.sort(np.random.default_rng(0xA71).choice(np.nonzero(inside)[0], 200, replace=False))
+    _subset_against_fp64(r, ltf, picks, tmpl)
+    assert np.array_equal(ltf["row"], pkg.abi.reduce_capture_records(ltf["records"], r["d"]))
+
+
+# ---- scoring refined positions
+def _score_window(eng, r, o, window):
+    """Engine.score_packets and stream.score_packets on the same records with a window: the device totals"""
+    from ofdm_amd.stream import score_packets
+    dev_out = eng.score_packets(r["words"], r["d"], o, positions=r["pos_dev"], window=window)
+    scores, totals = dev_out["scores"].cpu().numpy(), dev_out["totals"].cpu().numpy()
+    rw = o["d_words"][:o["count"]].cpu().numpy().view(np.uint32)
+    host = score_packets(r["pos"], r["words"].cpu().numpy().view(np.uint32), o["positions"], rw, window=window)
+    assert np.array_equal(scores[:, 0], host["rx_index"]) and np.array_equal(scores[:, 1], host["bit_err"])
+    assert np.array_equal(totals, host["totals"])
+    return totals
+
+
+def test_scoring_refined_positions(eng, pkg, timed, recs):
+    from ofdm_amd.stream import SCORE_MAX_WINDOW
+    abi = pkg.abi
+    r = recs["B"]
+    none, ltf = timed["B"]["none"], timed["B"]["ltf"]
+    nearest = int(np.diff(ltf["positions"]).min())
+    exact, default = _score_window(eng, r, ltf, (16, 16)), _score_window(eng, r, ltf, (8, 40))
+    widest = _score_window(eng, r, ltf, (0, SCORE_MAX_WINDOW))
+    coarse = _score_window(eng, r, none, (8, 40))
+    print(f"score B refined: neighbouring records at least {nearest} apart (coarse {int(np.diff(none['positions']).min())}); matched "
+          f"{exact[abi.S_MATCHED]} with (16, 16), {default[abi.S_MATCHED]} with (8, 40), {widest[abi.S_MATCHED]} with (0, 300), "
+          f"{coarse[abi.S_MATCHED]} without timing; bit errors {default[abi.S_BIT_ERR]} against {coarse[abi.S_BIT_ERR]}")
+    assert nearest >= 301 - 56 - 7 == 238
+    assert SCORE_MAX_WINDOW == 300
+    assert exact[abi.S_MATCHED] == default[abi.S_MATCHED] and np.array_equal(exact, default)
+    assert default[abi.S_MATCHED] >= coarse[abi.S_MATCHED]
+    assert widest[abi.S_MATCHED] >= default[abi.S_MATCHED]

@@ -2,7 +2,9 @@
 Engine.receive_stream(timing=), csrc/ofdm_stream_timing.hip): OFDM_TIMING_NONE byte for byte against
 ofdm_receive_stream_ex, noise-free streams that keep their positions, the refined positions of noisy and faded streams
 against stream.refine_timing in fp64 -- exactly -- with the decode at the refined position against the oracle, the
-stream's end, launch-shape independence, the link sweep and the stream command.
+stream's end, a tie of all candidates, an all-zero search window, the reference detector's coarse positions,
+launch-shape independence, the link sweep and the stream command.  tests/test_gpu_matlab_stream.py holds
+OFDM_TIMING_LTF_MATLAB, the same kernel with the other convention's template.
 
 Streams: detect_ref.noisy_stream under detect_ref.STREAM_SEEDS (25,420 to 27,194 samples, 290 packets in all) and
 timing_ref.clean_stream.  tests/test_timing_host.py checks on the CPU that on every one of the 290 packets the two
@@ -144,7 +146,7 @@ def test_timing_none_is_ofdm_receive_stream_ex(eng, pkg, oracle):
         cnt8 = torch.full((2,), -7, dtype=torch.int64, device="cuda")
         tim = torch.full((8, 16), 0x5A, dtype=torch.uint8, device="cuda")
         opts = abi.make_rx_opts("c")
-        for timing, d_timing in ((0, p(tim)), (2, None), (-1, p(tim))):
+        for timing, d_timing in ((0, p(tim)), (3, None), (-1, p(tim))):
             rc = lib.ofdm_receive_stream_timed(eng.ctx, p(x_dev), len(x_dev), C.byref(opts), None, timing, 1, 8, p(pk), p(cnt8),
                                                None, None, None, None, None, d_timing)
             assert rc == -1 and lib.ofdm_last_error(), timing
@@ -297,6 +299,79 @@ def test_stream_end(eng, runs, tmpl):
         assert oob.tolist() == [False] * k + [True]
         assert np.array_equal(cut["records"]["flags"], 2 * oob + 4 * (np.arange(k + 1) == k))
         assert cut["records"][:k].tobytes() == full["records"][:k].tobytes()
+
+
+# ---------------------------------------------------------------- 4b. ties, an all-zero window, the other detector
+TIE_VALUE = 0.25 + 0.125j
+
+
+def _two_packets_with_a_flat_window(oracle, value):
+    """Two noise-free packets of 2 data symbols; the second one's search window [p + 322, p + 640] (p its coarse
+    position, first sample + 16: behind the short training field, so the detection does not see it) holds one value"""
+    x, pos = ref.packet_stream(oracle, ref.rand_words(2, 2, 0x71E))
+    p = int(pos[1]) + 16
+    x[p + 322:p + tr.SPAN + 1] = value
+    return x.astype(np.complex64), pos, p
+
+
+def test_equal_candidates_take_the_smallest_shift(eng, oracle, tmpl):
+    """All 64 candidates of the second packet run the same chain on the same values, so their L are bit-equal on the
+    device and equal in fp64: the rule's tie-break (the butterfly's `ov == best && oj < bj`) must choose candidate 0."""
+    from ofdm_amd.stream import refine_timing
+    assert eng.set_long_message(MSG2) == 2
+    x, pos, p = _two_packets_with_a_flat_window(oracle, TIE_VALUE)
+    none, ltf = rx(eng, x, "none"), rx(eng, x, "ltf")
+    want = refine_timing(x, none["positions"], tmpl)
+    dev = quality_dev(ltf, want)
+    print(f"tie: coarse {(none['positions'] - pos).tolist()}, shifts {ltf['shift'].tolist()} (fp64 {want['shift'].tolist()}), quality "
+          f"{ltf['quality'].tolist()} (fp64 {want['quality'].tolist()}, deviation {dev:.3g}), spread of the fp64 L {np.ptp(want['metric'][1]):.3g}")
+    assert none["count"] == ltf["count"] == 2 and np.array_equal(none["positions"], pos + 16) and none["positions"][1] == p
+    assert np.ptp(want["metric"][1]) == 0.0 and want["metric"][1][0] > 0            # a tie of all 64 in fp64 as well
+    assert ltf["shift"].tolist() == want["shift"].tolist() == [0, -56]
+    assert np.array_equal(ltf["positions"], want["positions"]) and ltf["positions"][1] == p - 56
+    assert np.array_equal(ltf["coarse_pos"], none["positions"])
+    assert 0 < ltf["quality"][1] < 1 and dev <= 4 * TIMING_DEV_MEASURED
+    assert ltf["records"][:1].tobytes() == none["records"][:1].tobytes()
+
+
+def test_an_all_zero_window_keeps_the_position(eng, oracle, tmpl):
+    """every L is 0: the kernel's `lbest > 0` branch -- shift 0, quality exactly 0 and no NaN, the record untouched"""
+    from ofdm_amd.stream import refine_timing
+    assert eng.set_long_message(MSG2) == 2
+    x, pos, p = _two_packets_with_a_flat_window(oracle, 0.0)
+    assert not x[p + 322:p + 641].any() and x[p + 321] != 0
+    none, ltf = rx(eng, x, "none"), rx(eng, x, "ltf")
+    want = refine_timing(x, none["positions"], tmpl)
+    print(f"zero window: shifts {ltf['shift'].tolist()}, quality {ltf['quality'].tolist()} (fp64 {want['quality'].tolist()})")
+    assert none["count"] == ltf["count"] == 2 and none["positions"][1] == p
+    assert want["shift"].tolist() == [0, 0] and want["quality"][1] == 0.0
+    assert ltf["shift"].tolist() == [0, 0] and ltf["quality"][1] == 0.0 and np.isfinite(ltf["quality"]).all()
+    assert ltf["quality"][0] > 0.89 and quality_dev(ltf, want) <= 4 * TIMING_DEV_MEASURED
+    assert np.array_equal(ltf["coarse_pos"], none["positions"]) and np.array_equal(ltf["positions"], none["positions"])
+    assert ltf["records"].tobytes() == none["records"].tobytes()
+    assert same_bits(ltf["bits"], none["bits"]) and same_bits(ltf["eq"], none["eq"])
+
+
+@pytest.mark.parametrize("key", [(2, 25, 0.0, False), (15, 14, 40e3, False)])
+def test_timing_under_the_reference_detector(eng, oracle, tmpl, key):
+    """detector="reference" with timing="ltf": the positions are the fp64 rule on that detector's coarse positions"""
+    from ofdm_amd.stream import refine_timing
+    d = key[0]
+    assert eng.set_long_message(" " * (12 * d)) == d
+    x, pos = ref.noisy_stream(oracle, *key, ref.STREAM_SEEDS[key])
+    none, ltf = rx(eng, x, "none", detector="reference"), rx(eng, x, "ltf", detector="reference")
+    want = refine_timing(x, none["positions"], tmpl)
+    dev, gap = quality_dev(ltf, want), tr.top_gap(want["metric"]).min()
+    off, _ = tr.offsets(ltf["positions"], pos)
+    print(f"reference detector {key}: {ltf['count']} packets of {len(pos)}, shifts {sorted(set(ltf['shift'].tolist()))}, refined "
+          f"{int(off.min())}..{int(off.max())}, quality deviation {dev:.3g}, smallest gap {gap:.3g}")
+    assert ltf["count"] == ltf["found"] == none["count"] == len(pos) and ltf["shift"].any()
+    assert gap > 1e-4                                                 # what lets the positions be demanded exactly
+    assert np.array_equal(ltf["coarse_pos"], none["positions"])
+    assert np.array_equal(ltf["positions"], want["positions"]) and np.array_equal(ltf["shift"], want["shift"])
+    assert (off == 16).all() and dev <= 4 * TIMING_DEV_MEASURED
+    keep = np.nonzero(ltf["shift"] == 0)[0]
+    assert ltf["records"][keep].tobytes() == none["records"][keep].tobytes() and same_bits(ltf["eq"][keep], none["eq"][keep])
 
 
 # ---------------------------------------------------------------- 5. launch shapes

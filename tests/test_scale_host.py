@@ -26,7 +26,7 @@ def test_mirrored_constants_are_the_sources(pkg):
             m = re.findall(rf"^constexpr int {const} = (\d+);", text, re.M)
             assert m == [str(value)], (name, const, m, value)
             seen += 1
-    assert seen == 11
+    assert seen == 13
     # samples per channel quad: the tile is CH_QUAD quads' worth of samples per thread
     m = re.findall(r"^constexpr int CH_TILE = (\d+) \* CH_THREADS;", (CSRC / "ofdm_channel.hip").read_text(), re.M)
     assert m == [str(gs.CH_QUAD)] and gs.CH_TILE == 1024
@@ -39,6 +39,10 @@ def test_mirrored_constants_are_the_sources(pkg):
         assert f"(int64_t){prefix}_BLOCKS_PER_CU * c->cus" in text and f"{prefix}_GROUP_SYMS / opts->n_data" in text
     chan = (CSRC / "ofdm_channel.hip").read_text()
     assert "std::min<int64_t>(a.tiles, CH_MAX_GRID)" in chan and "(n_tx + SC_THREADS - 1) / SC_THREADS" in chan
+    timing = (CSRC / "ofdm_stream_timing.hip").read_text()
+    assert "(r.max_packets + TM_WAVES - 1) / TM_WAVES" in timing
+    assert "std::min<int64_t>(blocks, TM_BLOCKS_PER_CU * (int64_t)c->cus)" in timing
+    assert "i += (int64_t)gridDim.x * TM_WAVES" in timing and "__launch_bounds__(64 * TM_WAVES)" in timing
     abi = pkg.abi
     assert abi.STREAM_TILE == gs.DETECT_TILE and abi.CHANNEL_TILE == gs.CH_TILE
     assert [abi.packet_len(d) for d in gs.DS] == [gs.packet_len(d) for d in gs.DS]
@@ -69,7 +73,8 @@ def test_the_recordings_reach_their_branches_on_256_cus():
 
 @pytest.mark.parametrize("d", gs.DS)
 def test_every_payload_row_alone_is_found_once_at_offset_16(pkg, oracle, d):
-    from ofdm_amd.stream import select_packets
+    from detect_ref import band_is_harmless
+    from ofdm_amd.stream import detection_metric, select_packets
     rows = gs.rows_of(d)
     assert rows.shape == (gs.N, 3 * d)
     plen = gs.packet_len(d)
@@ -87,6 +92,10 @@ def test_every_payload_row_alone_is_found_once_at_offset_16(pkg, oracle, d):
             margin = min(margin, float(np.abs(m[ok] - 0.75).min()))
             fronts.append(len(sel["fronts"]))
             last_conf += int(sel["flags"][0] != 0)
+            # the conjugate detector places the row alike, and no decision of its lies in the band (a position may)
+            mc = detection_metric(x, "conjugate")
+            assert select_packets(mc)["positions"].tolist() == [g + gs.OFFSET], (d, k, g)
+            assert band_is_harmless(mc, 0.75, BAND), (d, k, g)
     print(f"D {d}: {gs.N} rows x 2 gaps, {np.mean(fronts):.2f} fronts per packet, LAST_FRONT on {last_conf} packets, "
           f"nearest position to the threshold {margin:.3g} away (band {BAND:.3g})")
     assert margin > BAND

@@ -161,6 +161,87 @@ def test_refined_positions_decode_better(pkg, oracle, tmpl):
     assert er < ec / 10
 
 
+# ---------------------------------------------------------------- 6b. MATLAB-convention recordings
+@pytest.fixture(scope="module")
+def tmpl_m(pkg, oracle):
+    return tr.template(oracle, "matlab")
+
+
+def test_matlab_template_is_the_c_template_rotated_by_half_a_period(pkg, oracle, tmpl, tmpl_m):
+    from ofdm_amd import stream
+    assert np.array_equal(tmpl_m, np.roll(tmpl, -64)) and not np.array_equal(tmpl_m, tmpl)
+    for d in (1, 2, 5, 15):
+        for seed in (100 + d, 200 + d):                               # two payloads
+            bits = ref.bits_of(ref.rand_words(d, 1, seed))[0]
+            wm, wc = (oracle.frame_waveform(bits, conv, True, 1) for conv in ("matlab", "c"))
+            assert np.array_equal(stream.ltf_template(wm), np.roll(tmpl, -64)), (d, seed)     # exactly 0.0 difference
+            k = np.arange(128)
+            assert np.array_equal(wm[394 + k], wc[394 + (k + 64) % 128]), (d, seed)
+            # the short training field is the same up to rounding (an fp32 step of the peak): detection does not see
+            # the convention
+            assert np.abs(wm[:320] - wc[:320]).max() <= 2.0 ** -23 * np.abs(wc).max(), (d, seed)
+
+
+@pytest.mark.parametrize("d,cfo", tr.CLEAN_CASES)
+def test_noise_free_matlab_positions_do_not_move(pkg, oracle, tmpl, tmpl_m, d, cfo):
+    """under the MATLAB template; and the signature of the defect this value exists for: at 200 kHz the C template
+    does not leave a MATLAB-convention packet at its first sample + 16"""
+    from ofdm_amd.stream import refine_timing
+    words, x, pos = tr.clean_stream(oracle, d, cfo, conv="matlab")
+    coarse = tr.coarse_positions(x)
+    r, wrong = refine_timing(x, coarse, tmpl_m), refine_timing(x, coarse, tmpl)
+    print(f"matlab D {d} {cfo:9.0f} Hz: coarse {(coarse - pos).tolist()}, MATLAB template {(r['positions'] - pos).tolist()} quality "
+          f"{r['quality'].round(4).tolist()}; C template {(wrong['positions'] - pos).tolist()} quality {wrong['quality'].round(3).tolist()}")
+    assert len(coarse) == tr.CLEAN_PACKETS and np.array_equal(coarse, pos + 16)
+    assert np.array_equal(r["positions"], pos + 16) and not r["shift"].any()
+    assert ((r["quality"] > 0.89) & (r["quality"] <= 1.0)).all()
+    if cfo == 200e3:
+        assert not np.array_equal(wrong["positions"], pos + 16)
+        assert (wrong["quality"] < r["quality"]).all()
+        # what it costs: the oracle's decode has no bit error at the MATLAB template's positions (nor at the coarse ones)
+        truth = ref.bits_of(words)
+        err = lambda ps: sum(ref.oracle_bit_errors(oracle, x, int(p), truth[k]) for k, p in enumerate(ps))
+        ec, er, ew = err(coarse), err(r["positions"]), err(wrong["positions"])
+        print(f"matlab D {d} 200 kHz: bit errors coarse {ec}, MATLAB template {er}, C template {ew}")
+        assert ec == 0 and er == 0
+
+
+def test_timing_ltf_matlab_passes_the_argument_check(pkg):
+    """2 is a timing now: the call gets as far as everything ofdm_receive_stream_ex refuses, d_timing allowed"""
+    lib = pkg.load_library()
+    abi = pkg.abi
+    opts = abi.make_rx_opts("c")
+    fake = C.c_void_p(0x1000)                                         # never dereferenced: the call fails first
+    call = lambda so, d_timing: lib.ofdm_receive_stream_timed(
+        None, None, 100, C.byref(opts), None if so is None else C.byref(so), abi.TIMING["ltf-matlab"], 1, 4, None, None, None,
+        None, None, None, None, d_timing)
+    for d_timing in (None, fake):
+        assert call(None, d_timing) == -1 and b"ctx" in lib.ofdm_last_error()
+        assert call(abi.StreamOpts(2, 0.75), d_timing) == -1 and b"detector" in lib.ofdm_last_error()
+        assert call(abi.StreamOpts(1, 1.0), d_timing) == -1 and b"threshold" in lib.ofdm_last_error()
+
+
+def test_matlab_noisy_streams_are_placed_and_have_no_tie(pkg, oracle, tmpl_m):
+    """the conditions on detect_ref.MATLAB_SEEDS that concern the timing (conjugate detector)"""
+    from ofdm_amd.stream import refine_timing
+    gaps = []
+    for key in ref.MATLAB_SEEDS:
+        d, snr, cfo, faded = key
+        x, pos = ref.matlab_stream(oracle, key)
+        coarse = tr.coarse_positions(x)
+        r = refine_timing(x, coarse, tmpl_m)
+        off, _ = tr.offsets(r["positions"], pos)
+        gap = tr.top_gap(r["metric"])
+        print(f"matlab D={d:2d} {snr} dB {cfo:7.0f} Hz {'faded  ' if faded else 'unfaded'}: {len(coarse)} packets, refined "
+              f"{int(off.min())}..{int(off.max())}, smallest gap {gap.min():.3g}, quality {r['quality'].min():.3f}..{r['quality'].max():.3f}")
+        assert len(coarse) == ref.MATLAB_FOUND[key][0] and (r["quality"] > 0).all()
+        assert (gap > 1e-4).all()
+        assert ((off >= 16) & (off <= 18)).all() if faded else (off == 16).all()
+        gaps.append(float(gap.min()))
+    print(f"smallest relative gap between the two largest L on the six streams {min(gaps):.4g}")
+    assert min(gaps) > 2 * 0.034                                      # the GPU tests' hard bound is half the smallest gap
+
+
 # ---------------------------------------------------------------- 7. the header, the binding, the build
 def test_timing_header_is_exported_and_bound(pkg):
     abi = pkg.abi
@@ -186,25 +267,26 @@ def test_stream_timing_layout_matches_the_header(pkg, tmp_path):
     st = abi.StreamTiming
     src = tmp_path / "offsets.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ofdm_mi355x_timing.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %d %d %d %d %d\\n", sizeof(ofdm_stream_timing), '
+                   'int main(void) { printf("%zu %zu %zu %zu %d %d %d %d %d %d\\n", sizeof(ofdm_stream_timing), '
                    "offsetof(ofdm_stream_timing, coarse_pos), offsetof(ofdm_stream_timing, quality), "
                    "offsetof(ofdm_stream_timing, shift), OFDM_TIMING_NONE, OFDM_TIMING_LTF, OFDM_TIMING_BACK, "
-                   "OFDM_TIMING_FWD, OFDM_K_STREAM_TIMING); return 0; }\n")
+                   "OFDM_TIMING_FWD, OFDM_K_STREAM_TIMING, OFDM_TIMING_LTF_MATLAB); return 0; }\n")
     exe = tmp_path / "offsets"
     r = subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror", f"-I{ROOT / 'include'}", str(src), "-o", str(exe)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     got = [int(t) for t in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
     assert got == [16, st.coarse_pos.offset, st.quality.offset, st.shift.offset, abi.TIMING["none"], abi.TIMING["ltf"],
-                   abi.TIMING_BACK, abi.TIMING_FWD, abi.K_STREAM_TIMING]
-    assert got == [16, 0, 8, 12, 0, 1, 56, 8, 13]
+                   abi.TIMING_BACK, abi.TIMING_FWD, abi.K_STREAM_TIMING, abi.TIMING["ltf-matlab"]]
+    assert got == [16, 0, 8, 12, 0, 1, 56, 8, 13, 2]
     assert C.sizeof(st) == 16 and abi.K_STREAM_TIMING == abi.K_STREAM_DETECT_CONJ + 1
     dt = abi.stream_timing_dtype()
     assert dt.itemsize == 16 and [dt.fields[n][1] for n in ("coarse_pos", "quality", "shift")] == [0, 8, 12]
     from ofdm_amd import stream
     assert set(abi.TIMING) == set(stream.TIMINGS) and (abi.TIMING_BACK, abi.TIMING_FWD) == (stream.TIMING_BACK, stream.TIMING_FWD)
     assert stream.TIMING_CANDIDATES == 64
-    assert abi.timing_code("none") == 0 and abi.timing_code("ltf") == 1
+    assert abi.timing_code("none") == 0 and abi.timing_code("ltf") == 1 and abi.timing_code("ltf-matlab") == 2
+    assert tuple(abi.TIMING) == stream.TIMINGS == ("none", "ltf", "ltf-matlab")
     for bad in ("LTF", "fine", None, 1):
         with pytest.raises(ValueError):
             abi.timing_code(bad)
@@ -219,7 +301,7 @@ def test_timing_argument_errors_come_before_any_device_work(pkg):
     call = lambda timing, so=None, d_timing=None: lib.ofdm_receive_stream_timed(
         None, None, 100, C.byref(opts), None if so is None else C.byref(so), timing, 1, 4, None, None, None, None, None,
         None, None, d_timing)
-    for timing in (2, -1, 7):
+    for timing in (3, -1, 7):
         assert call(timing) == -1 and b"timing" in lib.ofdm_last_error(), timing
         assert call(timing, conj, fake) == -1 and b"timing" in lib.ofdm_last_error(), timing
     assert call(0, None, fake) == -1 and b"d_timing" in lib.ofdm_last_error()

@@ -17,17 +17,18 @@ SPAN = 640                      # a packet is refined only when p + 640 < n
 BENEFIT = dict(d=2, packets=216, snr_db=10.0, cfo_hz=40e3, words_seed=0x716, noise_seed=0x717)
 
 
-def template(oracle) -> np.ndarray:
-    """stream.ltf_template of the oracle's Transmitter() (one period, 2 data symbols): complex128 [256]"""
+def template(oracle, conv: str = "c") -> np.ndarray:
+    """stream.ltf_template of the oracle's Transmitter() (one period, 2 data symbols) under the transform convention
+    conv, "c" (OFDM_TIMING_LTF) or "matlab" (OFDM_TIMING_LTF_MATLAB): complex128 [256]"""
     from ofdm_amd.stream import ltf_template
-    return ltf_template(oracle.frame_waveform(ref.bits_of(ref.rand_words(2, 1, 1))[0], "c", True, 1))
+    return ltf_template(oracle.frame_waveform(ref.bits_of(ref.rand_words(2, 1, 1))[0], conv, True, 1))
 
 
-def clean_stream(oracle, d: int, cfo_hz: float):
-    """Four noise-free packets of d data symbols behind 500-sample gaps under a carrier offset: words, the fp64 stream
-    and the packets' first samples"""
+def clean_stream(oracle, d: int, cfo_hz: float, conv: str = "c"):
+    """Four noise-free packets of d data symbols (transform convention conv) behind 500-sample gaps under a carrier
+    offset: words, the fp64 stream and the packets' first samples"""
     words = ref.rand_words(d, CLEAN_PACKETS, 30 + d)
-    x, pos = ref.packet_stream(oracle, words, cfo_hz=cfo_hz)
+    x, pos = ref.packet_stream(oracle, words, cfo_hz=cfo_hz, conv=conv)
     return words, x, pos
 
 
