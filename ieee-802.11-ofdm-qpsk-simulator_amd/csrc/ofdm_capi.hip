@@ -239,7 +239,7 @@ int ofdm_ctx_destroy(ofdm_ctx *ctx) {
     for (auto ev : c->pool) hipEventDestroy(ev);
     if (c->tx_stream) hipStreamSynchronize(c->tx_stream);
     for (void *p : {(void *)c->d_ltf[0], (void *)c->d_ltf[1], (void *)c->d_ltf2_rows[0], (void *)c->d_ltf2_rows[1], c->d_tx, c->d_bits, c->d_cnt, c->d_scratch,
-                    c->d_scratch2, c->d_wave, c->d_tx2, c->d_bits2, c->d_work})
+                    c->d_scratch2, c->d_wave, c->d_tx2, c->d_bits2, c->d_work, c->d_philox})
         if (p) hipFree(p);
     for (hipEvent_t ev : {c->ev_start, c->ev_tx[0], c->ev_tx[1], c->ev_rx[0], c->ev_rx[1]})
         if (ev) hipEventDestroy(ev);
@@ -523,6 +523,23 @@ static int rx_common(Ctx *c, const ofdm_cfg *cfg, const void *d_tx, const void *
         if (!c->d_work) HIPOK(hipMalloc(&c->d_work, 256));
         a.work = (unsigned long long *)c->d_work;
         HIPOK(hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long), c->stream));
+        if (rx_pack_applies(*cfg)) {
+            // ordered on the stream behind the launches that read the table it replaces
+            static_assert(sizeof(c->h_philox) == sizeof(PhiloxWords[2][PACK_BLOCKS]), "table size");
+            const uint32_t key[3] = {a.k0, a.k1, (uint32_t)(first_frame >> 32)};
+            if (!c->d_philox) HIPOK(hipMalloc(&c->d_philox, sizeof(c->h_philox)));
+            if (!c->philox_valid || c->philox_stream != c->stream || std::memcmp(key, c->philox_key, sizeof key)) {
+                // the staging copy of an earlier upload has been consumed before it is overwritten
+                if (c->philox_valid) HIPOK(hipStreamSynchronize(c->philox_stream));
+                c->philox_valid = false;
+                pack_philox_table(key[0], key[1], key[2], *reinterpret_cast<PhiloxWords (*)[2][PACK_BLOCKS]>(c->h_philox));
+                HIPOK(hipMemcpyAsync(c->d_philox, c->h_philox, sizeof(c->h_philox), hipMemcpyHostToDevice, c->stream));
+                std::memcpy(c->philox_key, key, sizeof key);
+                c->philox_stream = c->stream;
+                c->philox_valid = true;
+            }
+            a.philox_words = (const PhiloxWords *)c->d_philox;
+        }
         c->tic(Ctx::K_RX);
         launch_rx(c->stream, a, *cfg, dump, grid);
         c->toc();

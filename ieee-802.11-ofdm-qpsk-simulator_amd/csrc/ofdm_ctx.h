@@ -59,6 +59,13 @@ struct Ctx {
     hipEvent_t ev_start = nullptr, ev_tx[2] = {nullptr, nullptr}, ev_rx[2] = {nullptr, nullptr};
     void *d_wave = nullptr;
     void *d_work = nullptr;          // K3c's work-item counter (one receiver launch in flight per context)
+    // K3c's table of lane-independent Philox words (pack_philox_table): a function of the seed and of the high word
+    // of the launch's first frame, so it is uploaded again only when one of them (or the stream) changes
+    void *d_philox = nullptr;
+    bool philox_valid = false;
+    uint32_t philox_key[3] = {0, 0, 0};
+    hipStream_t philox_stream = nullptr;
+    uint32_t h_philox[2 * 48 * 4] = {};
     // pinned host staging for the sweeps' counter read-back (a pageable destination costs HIP a staging copy kernel
     // and a host round trip per call); grown on demand, freed with the context
     void *h_cnt = nullptr;

@@ -91,6 +91,53 @@ __device__ __forceinline__ uint4 philox10_c2(const PhiloxHead &h, uint32_t c2, u
     return make_uint4(c0, c1, c2, c3);
 }
 
+// philox10_c2 with the lane-independent part of rounds 1-2 taken out.  Of a call's counter (c0, c1, c2, c3) only
+// c0 (the frame index's low word) and c3's SNR index differ between lanes and SNR points; c1 (its high word) and
+// the block index c2 are the same in every lane of a group of frames that does not straddle 2^32.  Round 1's
+// c2 half, M1 c2 and c0' = hi ^ c1 ^ k0, and with it round 2's product M0 c0' are then functions of (c1, c2, key)
+// alone: philox_words() computes, once per (c1, c2), the three words they contribute, each folded with the round
+// key it is XORed with:
+//   x = lo(M1 c2) ^ (k0 + W0)          round 2: n0 = hi(M1 n2) ^ x
+//   y = hi(M0 c0') ^ (k1 + W1)         round 2: n2 = c3 ^ y
+//   z = lo(M0 c0') ^ (k1 + 2 W1)       round 3: n2 = hi(M0 c0'') ^ z
+// PhiloxMid holds what round 2 needs of the lane's own half (round 2's product M1 n2 is common to every block
+// index), and the overload below starts at round 2's XORs (same output as philox10).
+struct PhiloxWords { uint32_t x, y, z, pad; };
+__host__ __device__ inline PhiloxWords philox_words(uint32_t c1, uint32_t c2, uint32_t k0, uint32_t k1) {
+    const uint64_t p1 = (uint64_t)PHILOX_M1 * c2;
+    const uint32_t c0n = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint64_t p0 = (uint64_t)PHILOX_M0 * c0n;
+    return {(uint32_t)p1 ^ (k0 + PHILOX_W0), (uint32_t)(p0 >> 32) ^ (k1 + PHILOX_W1),
+            (uint32_t)p0 ^ (k1 + 2u * PHILOX_W1), 0u};
+}
+struct PhiloxMid { uint32_t p1lo, p1hi, c3; };
+__device__ __forceinline__ PhiloxMid philox_mid(const PhiloxHead &h) {
+    const uint64_t p1 = (uint64_t)PHILOX_M1 * h.n2;
+    return {(uint32_t)p1, (uint32_t)(p1 >> 32), h.c3};
+}
+__device__ __forceinline__ uint4 philox10_c2(const PhiloxMid &m, uint32_t wx, uint32_t wy, uint32_t wz, uint32_t k0,
+                                             uint32_t k1) {
+    uint32_t c0 = m.p1hi ^ wx, c1 = m.p1lo, c2 = m.c3 ^ wy, c3;
+    k0 += 2u * PHILOX_W0; k1 += 2u * PHILOX_W1;
+    {
+        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0;
+        const uint64_t p1 = (uint64_t)PHILOX_M1 * c2;
+        const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
+        c0 = n0; c1 = (uint32_t)p1; c2 = (uint32_t)(p0 >> 32) ^ wz; c3 = (uint32_t)p0;
+        k0 += PHILOX_W0; k1 += PHILOX_W1;
+    }
+#pragma unroll
+    for (int r = 3; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0;
+        const uint64_t p1 = (uint64_t)PHILOX_M1 * c2;
+        const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
+        const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96);
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += PHILOX_W0; k1 += PHILOX_W1;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
 // Round keys k0 + r W0, k1 + r W1 (r = 0..9) held in VGPRs: a v_bitop3_b32 with an SGPR operand issues
 // at the slow rate, with three VGPR operands at the fast rate.  Built once per kernel
 // (asm v_mov: never rematerialised into SGPR form); 20 VGPRs.

@@ -15,7 +15,8 @@ constexpr int SYM_SAMPLES = 80;        // 64 + 16-sample cyclic prefix (OFDM.c:5
 //   tx  [n * pitch + s] = time sample n (0..79, CP first) of data symbol s = 2 * frame + d
 //   bits[k * pitch + s] = payload word k (MSB-first bits 32k..32k+31) of symbol s, k = 0..2;
 //                         rows k = 3..6: demap word k - 3 (ofdm_rxcommon.h demap_word)
-//                         rows k = 7..9: pair-order word k - 7 (ofdm_rxcommon.h pair_words)
+//                         rows k = 7..9: pair-order word k - 7 (ofdm_rxcommon.h pair_words; the packed Rayleigh
+//                         receiver's truth -- the packed AWGN receivers use the signs of the samples' spectra)
 // pitch = symbols rounded up to a whole wave plus one guard wave, so whole-wave reads and the
 // receivers' groups (LS: 42 symbols, packed: 128 symbols) stay inside the buffer.
 inline int64_t sym_pitch(int64_t n_frames) { return (2 * n_frames + 63) / 64 * 64 + 64; }
@@ -56,12 +57,19 @@ struct RxArgs {
     int64_t dump_frames;               // leading dimension of the dumps (frames)
     unsigned long long *stamps;        // OFDM_RX_STAMPS builds: cycles per receiver phase [5]
     unsigned long long *work;          // K3c: work items handed out past the first gridDim.x (zeroed per launch)
+    const PhiloxWords *philox_words;   // K3c: [2][PACK_BLOCKS] lane-independent Philox words (pack_philox_table)
     TxArgs nx;                         // K3c: the NEXT chunk's Tx batch, built in the group prologues (n_sym 0: none)
     int32_t nx_conv;                   // its ifft convention
     TxArgs own;                        // K3c: THIS launch's Tx batch (ofdm_txrx_frames), each group built by the
     int32_t own_conv;                  // items that read it, before its clean spectra (n_sym 0: none)
     float sigma[OFDM_MAX_SNR];
 };
+
+// K3c's SNR loop draws PACK_BLOCKS Philox blocks per frame: the LTF pair's 48..63, then the data windows' 84..99
+// and 104..119; the launch's table of their lane-independent words is in this order
+constexpr int PACK_BLOCKS = 48;
+constexpr uint32_t pack_block(int slot) { return slot < 16 ? 48u + slot : slot < 32 ? 84u + (slot - 16) : 104u + (slot - 32); }
+void pack_philox_table(uint32_t k0, uint32_t k1, uint32_t frame_hi, PhiloxWords (&out)[2][PACK_BLOCKS]);
 
 void launch_fft64(hipStream_t st, const float2 *in, float2 *out, int64_t n, int inverse, int conv);
 void launch_tx(hipStream_t st, const TxArgs &a, int conv);

@@ -81,7 +81,8 @@ __host__ __device__ constexpr int pair_bin(int p) {
     return K[p];
 }
 // Pair-order truth words of one symbol (Tx rows 7..9): for each pair p, bins k then 64 - k, each as
-// (b0, b0 ^ b1) MSB first -- 4 bits per pair, 8 pairs per word (the demap_word signs, D10).
+// (b0, b0 ^ b1) MSB first -- 4 bits per pair, 8 pairs per word (the demap_word signs, D10).  Read by the packed
+// Rayleigh receiver; the packed AWGN receivers take the same signs from the clean spectra (demap_bin).
 __host__ __device__ inline void pair_words(const uint32_t w[3], uint32_t t[3]) {
     t[0] = t[1] = t[2] = 0u;
     for (int p = 0; p < PACK_PAIRS; ++p)

@@ -102,16 +102,29 @@ __device__ __forceinline__ void clean_spectrum(const RxArgs &a, int64_t s, float
 }
 
 // Per-bin demap of one data symbol at one bin: u = Z / g with g > 0 (KIND 0: g = 1, KIND 2: g = 2r),
-// the truth signs walked out of t (2 bits, im then re), EVM and slicer errors (demap_sub's arithmetic,
-// ofdm_rxcommon.h).  DUMP: the equalised value and the decided bits of data subcarrier m.
-template <int KIND, bool DUMP>
-__device__ __forceinline__ void demap_bin(float2 u, float r, uint32_t &t, uint32_t sm, float &evm, uint32_t &em,
-                                          int m, float2 *dump_eq, uint32_t (&dbits)[3]) {
+// the truth signs, EVM and slicer errors (demap_sub's arithmetic, ofdm_rxcommon.h).  DUMP: the equalised value
+// and the decided bits of data subcarrier m.
+// The truth signs: WALK (the Rayleigh receiver, whose spectra are H' C) walks them out of the pair-order word t
+// (2 bits, im then re).  Otherwise they are the sign bits of the bin's clean components (sx, sy), which the pair
+// holds in registers for Y = C + N: a QPSK point is (+-1 +-j) / sqrt2 times the bin's constant sign cs ((-1)^k in
+// the C convention, +1 in MATLAB's), and u has the sign of C cs (KIND 0: u = cs Y; KIND 2: u = Lf Y conj(S) with
+// S ~ 2 Lf cs).  TBL is the v_bitop3 table of u ^ (sign & 0x80000000): 0x78 = a ^ (b & c) where cs = +1,
+// 0xD2 = a ^ (~b & c) where cs = -1.  Same 32 bits as the walked word gives for every batch whose rows 7..9 are
+// the bits of its samples (include/ofdm_mi355x.h).
+template <int KIND, bool DUMP, bool WALK, int TBL>
+__device__ __forceinline__ void demap_bin(float2 u, float r, uint32_t &t, float sx, float sy, uint32_t sm, float &evm,
+                                          uint32_t &em, int m, float2 *dump_eq, uint32_t (&dbits)[3]) {
     constexpr float cd = KIND == 2 ? 0.5f * INV_SQRT2 : INV_SQRT2;
-    const uint32_t ti = t, tr = dbl_u32(t);
-    t = dbl_u32(tr);
-    const uint32_t ur = __builtin_amdgcn_bitop3_b32(__float_as_uint(u.x), tr, sm, 0x78);
-    const uint32_t ui = __builtin_amdgcn_bitop3_b32(__float_as_uint(u.y), ti, sm, 0x78);
+    uint32_t ur, ui;
+    if constexpr (WALK) {
+        const uint32_t ti = t, tr = dbl_u32(t);
+        t = dbl_u32(tr);
+        ur = __builtin_amdgcn_bitop3_b32(__float_as_uint(u.x), tr, sm, 0x78);
+        ui = __builtin_amdgcn_bitop3_b32(__float_as_uint(u.y), ti, sm, 0x78);
+    } else {
+        ur = __builtin_amdgcn_bitop3_b32(__float_as_uint(u.x), __float_as_uint(sx), sm, TBL);
+        ui = __builtin_amdgcn_bitop3_b32(__float_as_uint(u.y), __float_as_uint(sy), sm, TBL);
+    }
     float ex, ey;
     if constexpr (KIND == 0) {
         ex = __uint_as_float(ur) - cd;
@@ -141,6 +154,18 @@ __device__ __forceinline__ Noise4 pack_noise(const PhiloxHead &hd, uint32_t c2, 
     if constexpr (std::is_same_v<KS, PhiloxKeysV>) o = philox10_c2(hd, c2, keys);
     else o = philox10_c2(hd, c2, keys, k1);
     return noise4_of(o, K);
+}
+
+// The same draw from the lane-independent words of a Philox block index (ofdm_device.h philox_words): w points at
+// the block's entry of the item's row of the launch's table (pack_philox_table), staged in LDS by the item's
+// prologue and read by broadcast where it is used.  (Read from the table itself with scalar loads, the loop's
+// lgkmcnt waits gave back all of the gain: c3 at the level of the per-lane rounds, profiles/r07/ab/README.md.)
+typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+static_assert(sizeof(PhiloxWords) == sizeof(u4v), "one 16-byte read per block");
+typedef __attribute__((address_space(3))) const u4v cwords;
+__device__ __forceinline__ Noise4 pack_noise(const PhiloxMid &md, cwords *w, uint32_t k0, uint32_t k1, float K) {
+    const u4v v = *w;
+    return noise4_of(philox10_c2(md, v.x, v.y, v.z, k0, k1), K);
 }
 
 #ifdef OFDM_PACK_STAMPS   // diagnostic build: s_memtime per item phase, per wave role, summed over the grid
@@ -179,7 +204,7 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
     __shared__ __attribute__((aligned(16))) float4 spec[PACK_PAIRS][2][PK_FRAMES];   // 48 KB: (C[k], C[64-k])
     __shared__ __attribute__((aligned(16))) float4 ce[PACK_PAIRS];                   // LS: FFT((-1)^n 2T[n])
     __shared__ __attribute__((aligned(16))) float4 fce[FADE ? PACK_PAIRS : 1][FADE ? PK_FRAMES : 1];  // 24 KB: H' FFT(2T)
-    __shared__ __attribute__((aligned(8))) uint32_t truth[3][PK_SYMS];               // pair-order words
+    __shared__ __attribute__((aligned(8))) uint32_t truth[FADE ? 3 : 1][FADE ? PK_SYMS : 2];   // pair-order words (Rayleigh)
     // flush_lanes' five slots per SNR point; for the first SACC_XQ points SUBN - 1 more copies: lane l adds into
     // copy l % SUBN, so that an SNR iteration's 5 x 64 same-address LDS atomics (the kernel's LDS bank-conflict
     // cycles) spread over SUBN addresses in distinct banks; the copies are summed before the flush
@@ -192,6 +217,7 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
         const int c = ln % SUBN;
         return SUBN > 1 && c > 0 && q < SACC_XQ ? &sacx[q][5 * (c - 1)] : sacc[q];
     };
+    __shared__ __attribute__((aligned(16))) u4v wlds[PACK_BLOCKS];   // the item's Philox words
     __shared__ uint32_t pf_dummy[64];                             // L2 warm-up destination (never read)
     // 8 B of LDS that a pruned option's array held in every measured build (round 6, profiles/r06/README.md): kept,
     // with its per-iteration address, so that the code objects stay byte-identical to the PMC-certified builds
@@ -246,6 +272,13 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
         const int sub = tail ? tw % S : 0, ns = tail ? S : 1;
         __syncthreads();                                   // every wave is done with the last group
         PK_STAMP(0);                                       // item-top barrier (waiting for the other waves)
+        // The lane-independent Philox words (ofdm_device.h philox_words) hold for one high word of the frame index:
+        // the item takes the table row of its group's (a launch's frames reach at most one multiple of 2^32, so it
+        // is row 0 or 1), and an item whose 64 frames straddle the multiple runs the per-lane rounds instead.
+        // Wave-uniform: the second instantiation of the SNR loop costs the first no select.
+        const uint64_t fg = a.first_frame + (uint64_t)(grp * PK_FRAMES);
+        const uint32_t row = (uint32_t)(fg >> 32) - (uint32_t)(a.first_frame >> 32);
+        const bool uniform_hi = (uint32_t)((fg + (PK_FRAMES - 1)) >> 32) == (uint32_t)(fg >> 32) && row < 2u;
         // group-invariant addresses are re-derived from the thread index here, not held across the SNR
         // loop (they would be the only values spilled)
         int t = tid;
@@ -274,10 +307,12 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
             clean_spectrum(a, grp * PK_SYMS + t, &spec[0][t & 1][t >> 1]);
         } else {
             const int j = t - PK_SYMS;
-            const uint32_t *src = a.bits + 7 * a.pitch + grp * PK_SYMS + j;
-            truth[0][j] = src[0];
-            truth[1][j] = src[a.pitch];
-            truth[2][j] = src[2 * a.pitch];
+            if constexpr (FADE) {      // the AWGN receivers take the truth signs from the clean spectra (demap_bin)
+                const uint32_t *src = a.bits + 7 * a.pitch + grp * PK_SYMS + j;
+                truth[0][j] = src[0];
+                truth[1][j] = src[a.pitch];
+                truth[2][j] = src[2 * a.pitch];
+            }
             if (j < 64) {                                  // wave 2: the next item
                 int nx = 0;
                 if (j == 0) nx = B + (int)atomicAdd(a.work, 1ull);
@@ -305,6 +340,8 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
                     else tx_symbol<OFDM_CONV_MATLAB>(ap->nx, sidx);
                 }
             }
+            if (uniform_hi && j >= 64 && j < 64 + PACK_BLOCKS)       // wave 3: the item's row
+                wlds[j - 64] = ((const u4v *)a.philox_words)[row * PACK_BLOCKS + (j - 64)];
             if constexpr (FADE) {      // the group's channel responses, a frame's 24 pairs split over waves 2 / 3
                 const int fr = j & 63;
                 const uint64_t ff = a.first_frame + (uint64_t)(grp * PK_FRAMES + fr);
@@ -337,6 +374,9 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
         const int64_t fl = grp * PK_FRAMES + lane;
         const bool valid = fl < a.n_frames;
         const uint64_t f = a.first_frame + (uint64_t)fl;
+        auto snr_loop = [&](auto fastc) __attribute__((always_inline)) {
+        constexpr bool FAST = decltype(fastc)::value;
+        cwords *wtab = (cwords *)&wlds[0];
         for (int q = wv + 4 * sub; q < a.n_snr; q += 4 * ns) {
             // LS AWGN: wave 2 warms L2 with the next item's rows at the start of its last SNR iteration, one
             // iteration before the next prologue reads them (warmed in the prologue, a whole item earlier, most
@@ -364,6 +404,14 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
             const float sigma = a.sigma[q];
             const uint32_t qs = STREAM_NOISE | (uint32_t)(a.q_base + q);
             const PhiloxHead hd = philox_head(flo, fhi, qs, a.k1);
+            const PhiloxMid md = philox_mid(hd);
+            // block index `blk` of table slot `slot` (a literal); the words' LDS address goes through an opaque copy
+            // where a stage starts, so that the stage's reads stay inside it (as sp's do)
+            cwords *wt = wtab;
+            auto noise = [&](uint32_t blk, int slot, float Kn) __attribute__((always_inline)) {
+                if constexpr (FAST) return pack_noise(md, wt + slot, a.k0, a.k1, Kn);
+                else return pack_noise(hd, blk, a.k0, a.k1, Kn);
+            };
             // ---- LTF pair noise (LS): e[n] = sqrt2 sigma x Gaussian 192 + n (block 48 + n/4), packed as
             // z[m] = e'[2m] + j e'[2m+1] with e'[n] = (-1)^n e[n]; radix-2 stage fused, then two dif4<16>
             float2 z[64];      // z[0..31] used
@@ -375,12 +423,13 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
                 static_for<0, 4>([&](auto ic) {
                     constexpr int i = decltype(ic)::value;
                     uint32_t tg = 48u + 2 * i;
-                    opaque(tg);
+                    if constexpr (FAST) opaque(wt);
+                    else opaque(tg);
                     // blocks b = 2i, 2i+1 (z[4i..4i+3]) and b + 8 (z[4i+16..4i+19])
                     static_for<0, 2>([&](auto hc) {
                         constexpr int h = decltype(hc)::value;
-                        const Noise4 lo = pack_noise(hd, tg + h, a.k0, a.k1, KE);
-                        const Noise4 hi = pack_noise(hd, tg + 8 + h, a.k0, a.k1, KE);
+                        const Noise4 lo = noise(tg + h, 2 * i + h, KE);
+                        const Noise4 hi = noise(tg + 8 + h, 2 * i + 8 + h, KE);
                         constexpr int m = 4 * i + 2 * h;
                         z[m] = make_float2(lo.r0 * lo.c0, -(lo.r0 * lo.s0));
                         z[m + 1] = make_float2(lo.r1 * lo.c1, -(lo.r1 * lo.s1));
@@ -417,11 +466,12 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
             static_for<0, 4>([&](auto gc) {
                 constexpr int g = decltype(gc)::value;
                 uint32_t tg = 84u + g;
-                opaque(tg);
+                if constexpr (FAST) opaque(wt);
+                else opaque(tg);
                 static_for<0, 4>([&](auto Qc) {
                     constexpr int Q = decltype(Qc)::value;
-                    const Noise4 n0 = pack_noise(hd, tg + 4 * Q, a.k0, a.k1, K);
-                    const Noise4 n1 = pack_noise(hd, tg + 20 + 4 * Q, a.k0, a.k1, K);
+                    const Noise4 n0 = noise(tg + 4 * Q, 16 + g + 4 * Q, K);
+                    const Noise4 n1 = noise(tg + 20 + 4 * Q, 32 + g + 4 * Q, K);
                     const float d0[4] = {n0.r0 * n0.c0, n0.r0 * n0.s0, n0.r1 * n0.c1, n0.r1 * n0.s1};
                     const float d1[4] = {n1.r0 * n1.c0, n1.r0 * n1.s0, n1.r1 * n1.c1, n1.r1 * n1.s1};
                     static_for<0, 4>([&](auto ic) {
@@ -445,9 +495,10 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
             }
             uint32_t db0[3] = {0u, 0u, 0u}, db1[3] = {0u, 0u, 0u};
             lcf4 *sp = (lcf4 *)&spec[0][0][lane];
-            lcu2 *tw = (lcu2 *)&truth[0][2 * lane];
+            lcu2 *tw = (lcu2 *)&truth[0][FADE ? 2 * lane : 0];
             lcf4 *fp = (lcf4 *)&fce[0][FADE ? lane : 0];   // per-iteration address: the loads stay in the loop
-            opaque(sp); opaque(tw);
+            opaque(sp);
+            if constexpr (FADE) opaque(tw);
             if constexpr (FADE) opaque(fp);
             uint32_t sm;
             asm volatile("v_mov_b32 %0, 0x80000000" : "=v"(sm));
@@ -479,7 +530,7 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
             auto pair = [&](auto pc) {
                 constexpr int p = decltype(pc)::value;
                 constexpr int k = pair_bin(p), k2 = 64 - k;
-                if constexpr ((p & 7) == 0) {
+                if constexpr (FADE && (p & 7) == 0) {
                     const u2v tt = tw[(p >> 3) * (PK_SYMS / 2)];
                     t0 = tt.x; t1 = tt.y;
                 }
@@ -512,10 +563,12 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
                     constexpr float cs = (CONV == OFDM_CONV_C && (k & 1)) ? -1.0f : 1.0f;   // k, k2 same parity
                     u0k = cscale(y0k, cs); u0m = cscale(y0m, cs); u1k = cscale(y1k, cs); u1m = cscale(y1m, cs);
                 }
-                demap_bin<KIND, DUMP>(u0k, rk, t0, sm, evm, em, data_index(k), deq0, db0);
-                demap_bin<KIND, DUMP>(u0m, rm, t0, sm, evm, em, data_index(k2), deq0, db0);
-                demap_bin<KIND, DUMP>(u1k, rk, t1, sm, evm, em, data_index(k), deq1, db1);
-                demap_bin<KIND, DUMP>(u1m, rm, t1, sm, evm, em, data_index(k2), deq1, db1);
+                // the expected signs: those of C cs (k and 64 - k have the same parity)
+                constexpr int TBL = (CONV == OFDM_CONV_C && (k & 1)) ? 0xD2 : 0x78;
+                demap_bin<KIND, DUMP, FADE, TBL>(u0k, rk, t0, c0.x, c0.y, sm, evm, em, data_index(k), deq0, db0);
+                demap_bin<KIND, DUMP, FADE, TBL>(u0m, rm, t0, c0.z, c0.w, sm, evm, em, data_index(k2), deq0, db0);
+                demap_bin<KIND, DUMP, FADE, TBL>(u1k, rk, t1, c1.x, c1.y, sm, evm, em, data_index(k), deq1, db1);
+                demap_bin<KIND, DUMP, FADE, TBL>(u1m, rm, t1, c1.z, c1.w, sm, evm, em, data_index(k2), deq1, db1);
                 if constexpr ((p & 3) == 3) {
                     // 16 decisions: im errors at even bit positions, re errors at odd
                     ax += __popc(em);
@@ -546,6 +599,9 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
             frame_metrics(acc, KIND == 2 ? 4.0f * evm : evm, be, ax);
             flush_lanes(acc, valid, slots(q, lane));
         }
+        };
+        if (uniform_hi) snr_loop(std::true_type{});
+        else snr_loop(std::false_type{});
         PK_STAMP(4);                                     // SNR loop
     }
     if constexpr (SUBN > 1) {       // fold the copies into sacc
@@ -619,10 +675,20 @@ bool rx_pack_applies(const ofdm_cfg &cfg) {
     return cfg.channel == OFDM_CHAN_AWGN;
 }
 
+// The launch's table of lane-independent Philox words (RxArgs::philox_words): rows for the high word of the
+// launch's first frame and for the next one, each the loop's PACK_BLOCKS block indices in table-slot order.
+void pack_philox_table(uint32_t k0, uint32_t k1, uint32_t frame_hi, PhiloxWords (&out)[2][PACK_BLOCKS]) {
+    for (int r = 0; r < 2; ++r)
+        for (int s = 0; s < PACK_BLOCKS; ++s) out[r][s] = philox_words(frame_hi + (uint32_t)r, pack_block(s), k0, k1);
+}
+
 void launch_rx_pack(hipStream_t st, const RxArgs &a, const ofdm_cfg &cfg, bool dump, unsigned grid) {
     if (cfg.est == OFDM_EST_LS && cfg.channel == OFDM_CHAN_RAYLEIGH4)
         launch_pack_t<2, OFDM_CONV_C, OFDM_CHAN_RAYLEIGH4>(st, a, dump, grid);           // conv via a.ltf
-    else if (cfg.est == OFDM_EST_LS) launch_pack_t<2, OFDM_CONV_C>(st, a, dump, grid);
+    else if (cfg.est == OFDM_EST_LS) {             // the convention of the truth signs' table (demap_bin)
+        if (cfg.conv == OFDM_CONV_C) launch_pack_t<2, OFDM_CONV_C>(st, a, dump, grid);
+        else launch_pack_t<2, OFDM_CONV_MATLAB>(st, a, dump, grid);
+    }
     else launch_rx_pack_ideal(st, a, cfg, dump, grid);
 }
 

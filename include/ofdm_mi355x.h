@@ -133,7 +133,10 @@ int ofdm_fft64(ofdm_ctx *ctx, const void *d_in, void *d_out, int64_t n, int inve
  * layout: d_tx[n * pitch + s] = sample n (0..79, CP first) as float2, d_bits[k * pitch
  * + s] = payload word k (MSB-first bits, k = 0..2) as uint32, rows k = 3..6 the receivers' demap words
  * (truth signs in FFT sub-block order), rows k = 7..9 the packed receivers' truth words (Hermitian bin
- * pair order), pitch = tx_bytes / (80 * 8).  Buffer sizes:
+ * pair order), pitch = tx_bytes / (80 * 8).  The packed AWGN receivers (real noise, AWGN
+ * channel, either estimator) score against the signs of the batch's own samples -- the sign bits of each data
+ * bin of FFT((-1)^n d_tx rows 16..79), times (-1)^bin under OFDM_CONV_C -- and do not read rows 7..9; for every
+ * batch this library builds those signs are rows 7..9.  The packed Rayleigh receiver reads rows 7..9.  Buffer sizes:
  * ofdm_tx_bytes(n_frames, &tx_bytes, &bits_bytes); at most 2^23 frames per batch. */
 int ofdm_tx_bytes(int64_t n_frames, int64_t *tx_bytes, int64_t *bits_bytes);
 int ofdm_tx_frames(ofdm_ctx *ctx, const ofdm_cfg *cfg, uint64_t first_frame, int64_t n_frames,
