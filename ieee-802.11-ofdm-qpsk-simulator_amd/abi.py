@@ -37,6 +37,7 @@ K_CHANNEL, K_SCORE = 8, 9                                        # OFDM_K_CHANNE
 K_FADE, K_DRAW_TAPS = 10, 11                                     # OFDM_K_FADE, OFDM_K_DRAW_TAPS (ofdm_mi355x_fading.h)
 K_STREAM_DETECT_CONJ = 12                                        # OFDM_K_STREAM_DETECT_CONJ (ofdm_mi355x_detect.h)
 K_STREAM_TIMING = 13                                             # OFDM_K_STREAM_TIMING (ofdm_mi355x_timing.h)
+K_STREAM_DECODE_TRACK = 14                                       # OFDM_K_STREAM_DECODE_TRACK (ofdm_mi355x_track.h)
 
 # every entry point of the header, with ctypes argument types
 _V = C.c_void_p
@@ -164,6 +165,16 @@ TIMING_EXPORTS = tuple(_TIMING_SIGS)
 TIMING = {"none": 0, "ltf": 1, "ltf-matlab": 2}  # OFDM_TIMING_NONE, OFDM_TIMING_LTF, OFDM_TIMING_LTF_MATLAB
 TIMING_BACK, TIMING_FWD = 56, 8                  # OFDM_TIMING_BACK, OFDM_TIMING_FWD: shifts -56 .. +7
 
+# the extension header include/ofdm_mi355x_track.h (pilot phase tracking in the stream receiver's decode); the export
+# lists above and ABI_VERSION do not change with it
+TRACK_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_track.h"
+_TRACK_SIGS = {
+    "ofdm_receive_stream_tracked": (C.c_int, [_V, _V, C.c_int64, _V, _V, C.c_int, C.c_int, C.c_int, C.c_int64, _V, _V, _V,
+                                              _V, _V, _V, _V, _V, _V]),
+}
+TRACK_EXPORTS = tuple(_TRACK_SIGS)
+TRACKING = {"none": 0, "pilots": 1}              # OFDM_TRACK_NONE, OFDM_TRACK_PILOTS
+
 
 class OfdmError(RuntimeError):
     pass
@@ -263,6 +274,13 @@ def timing_code(timing: str) -> int:
     if not isinstance(timing, str) or timing not in TIMING:
         raise ValueError(f"timing must be one of {tuple(TIMING)}, got {timing!r}")
     return TIMING[timing]
+
+
+def tracking_code(tracking: str) -> int:
+    """OFDM_TRACK_* of "none" or "pilots"; ValueError for anything else"""
+    if not isinstance(tracking, str) or tracking not in TRACKING:
+        raise ValueError(f"tracking must be one of {tuple(TRACKING)}, got {tracking!r}")
+    return TRACKING[tracking]
 
 
 class StreamPacket(C.Structure):
@@ -374,7 +392,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
     for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS,
-                              **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS, **_TIMING_SIGS}.items():
+                              **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS, **_TIMING_SIGS, **_TRACK_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -25,6 +25,9 @@
 // (ofdm_stream_detect.h): another detection launch, then the selection and decode launches of this file.
 // ofdm_receive_stream_timed (ofdm_stream_timing.hip) adds a refiner through the same door: one launch of its own
 // between stream_select_kernel<2> and stream_decode_kernel that rewrites packet_pos.
+// ofdm_receive_stream_tracked (ofdm_stream_track.hip) adds a decoder: its own kernel in place of stream_decode_kernel,
+// launched with the same arguments, grid and LDS.  The decode's constants, DecArgs and the sdec_ helpers live in
+// ofdm_stream_decode.h for the two decode kernels.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -32,6 +35,7 @@
 #include "ofdm_ctx.h"
 #include "ofdm_rxcommon.h"
 #include "ofdm_stream_detect.h"
+#include "ofdm_stream_decode.h"
 
 namespace ofdm {
 
@@ -49,19 +53,8 @@ constexpr int SS_THREADS = 256;           // slots per block of the selection ke
 constexpr int SS_SLOT = 301;              // positions per slot: fronts are at least 301 apart
 constexpr int SS_SCAN_THREADS = 1024;
 
-constexpr int SDEC_MAX_DATA = LONG_MAX_FRAMES;
 constexpr int SDEC_MAX_WAVES = 8;                     // 512 threads: two waves per SIMD, 256 VGPRs each
-constexpr size_t SDEC_LDS_PER_CU = 160 * 1024;
-constexpr int SDEC_ACC_WORDS = OFDM_NCOUNTERS;
-constexpr double SDEC_TS = 1.0 / 20e6;                // OFDM.c:16-17
-constexpr int SDEC_SPEC_PITCH = 130;                  // floats per parked spectrum (as capture_rx_kernel)
-constexpr int SDEC_LOADS = 8;                         // 16-byte loads a lane keeps in flight while staging (all of a 2-symbol packet's)
-constexpr uint64_t sdec_ltf_neg() {
-    uint64_t v = 0;
-    for (int b = 0; b < 64; ++b) v |= (uint64_t)(ltf_sign(b) < 0) << b;
-    return v;
-}
-constexpr uint64_t SDEC_LTF_NEG = sdec_ltf_neg();
+static_assert(SDEC_MAX_WAVES == SDEC_BLOCK_WAVES, "the block stream_receive sizes fits both decode kernels' launch bounds");
 static_assert(sizeof(ofdm_stream_packet) == 64, "ofdm_stream_packet is 64 bytes");
 
 // DetArgs: ofdm_stream_detect.h (shared with the detectors of ofdm_stream_conj.hip)
@@ -280,22 +273,6 @@ __global__ __launch_bounds__(PHASE == 1 ? SS_SCAN_THREADS : SS_THREADS) void str
     }
 }
 
-struct DecArgs {
-    const float2 *x;
-    int64_t n;
-    const int64_t *count;    // d_count: [1] records to decode
-    ofdm_stream_packet *pk;
-    uint32_t *bits;
-    float2 *eq;
-    unsigned long long *counters;
-    int32_t n_data, float_cfo;
-    int32_t plane;           // floats per plane (2 nfr + 19 rounded up to 4)
-    int32_t wave_floats;     // floats per wave: two planes and fr[]
-    float taps[21];
-    uint32_t dtable[4 * SDEC_MAX_DATA];
-    uint32_t ztable[SDEC_MAX_DATA];   // per data symbol, were it all zeros: bit errors | slicer axis errors << 16 (stream_zero_errors)
-};
-
 // The errors of a data symbol that arrives as 64 exact zeros (its window lies wholly past the stream's end), as
 // ofdm_captures.hip counts them: the reference's slicer decides "-" on both axes for a zero (OFDM.c:858-866), the
 // demapper (1, 0) for every pair, so the counts depend on the payload alone.  w: the symbol's 96 payload bits, MSB
@@ -309,32 +286,6 @@ static uint32_t stream_zero_errors(const uint32_t w[3]) {
         ax += (uint32_t)(b0 == b1) + (uint32_t)(b0 == 0u);
     }
     return be | (ax << 16);
-}
-
-// LDS ordering between the lanes of one wave (the block's other waves run other packets)
-__device__ __forceinline__ void sdec_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ float sdec_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// rotate by exp(-j 2 pi f Ts i): the phase in revolutions in fp64, range-reduced, then v_sin / v_cos (OFDM.c:802,825)
-__device__ __forceinline__ float2 sdec_rot(float2 v, double f_ts, int i) {
-    const double rev = -f_ts * (double)i;
-    const float fr = (float)(rev - rint(rev));
-    const float s = __builtin_amdgcn_sinf(fr), c = __builtin_amdgcn_cosf(fr);
-    return make_float2(v.x * c - v.y * s, v.x * s + v.y * c);
-}
-// frame sample ii is one the receiver uses: STF tail [80, 112), LTF pair [192, 320), data symbols past their prefixes
-__device__ __forceinline__ bool sdec_needed(int ii) {
-    if (ii < 192) return ii >= 80 && ii < 112;
-    if (ii < 320) return true;
-    const int r = (ii - 320) % 80;
-    return r >= 16;
 }
 
 // capture_rx_kernel's chain from the matched filter on (ofdm_captures.hip), restated here so that that kernel's
@@ -596,7 +547,8 @@ static void stream_taps(float out[21]) {
 // with its own halo; everything after the bitmap -- selection, compaction, decode -- is the same launches either way.
 int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts, int payload,
                    int64_t max_packets, void *d_packets, void *d_count, void *d_bits, void *d_eq, void *d_counters,
-                   void *d_metric, void *d_cross, const StreamDetector *det, const StreamRefiner *ref) {
+                   void *d_metric, void *d_cross, const StreamDetector *det, const StreamRefiner *ref,
+                   const StreamDecoder *dec) {
     const int halo = det ? det->halo : 47;
     if (!c) return set_error(OFDM_E_ARG, "ctx is NULL");
     if (!opts) return set_error(OFDM_E_ARG, "opts is NULL");
@@ -719,6 +671,14 @@ int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_
     // the packet count stays on the device: enough blocks for max_packets, at most two per CU; the waves loop over d_count
     const int64_t blocks = (max_packets + W - 1) / W;
     const dim3 grid((unsigned)std::min<int64_t>(blocks, 2 * (int64_t)c->cus));
+    if (dec) {                                                       // another decode kernel on the same arguments
+        c->tic(dec->kernel);
+        dec->launch(dec, grid, dim3(64 * W), lds, c->stream, da, table);
+        c->toc();
+        e = hipGetLastError();
+        if (e != hipSuccess) return set_error(OFDM_E_HIP, "%s launch: %s", dec->name, hipGetErrorString(e));
+        return OFDM_OK;
+    }
     c->tic(OFDM_K_STREAM_DECODE);
     if (da.bits || da.eq) hipLaunchKernelGGL(stream_decode_kernel<true>, grid, dim3(64 * W), lds, c->stream, da);
     else hipLaunchKernelGGL(stream_decode_kernel<false>, grid, dim3(64 * W), lds, c->stream, da);

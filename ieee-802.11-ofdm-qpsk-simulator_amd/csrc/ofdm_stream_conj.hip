@@ -220,10 +220,11 @@ static void launch_thr(const StreamDetector *det, dim3 grid, hipStream_t stream,
     else hipLaunchKernelGGL(stream_detect_thr_kernel<false>, grid, dim3(CD_THREADS), 0, stream, a, det->threshold);
 }
 
-// ofdm_receive_stream_ex's body; ref (ofdm_stream_detect.h) is handed on to stream_receive
+// ofdm_receive_stream_ex's body; ref and dec (ofdm_stream_detect.h) are handed on to stream_receive
 int stream_receive_ex(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
                       const ofdm_stream_opts *sopts, int payload, int64_t max_packets, void *d_packets, void *d_count,
-                      void *d_bits, void *d_eq, void *d_counters, void *d_metric, void *d_cross, const StreamRefiner *ref) {
+                      void *d_bits, void *d_eq, void *d_counters, void *d_metric, void *d_cross, const StreamRefiner *ref,
+                      const StreamDecoder *dec) {
     int detector = OFDM_DETECT_REFERENCE;
     float thr = OFDM_DETECT_THRESHOLD;
     if (sopts) {
@@ -238,7 +239,7 @@ int stream_receive_ex(Ctx *c, const void *d_samples, int64_t n_samples, const of
     // the defaults are ofdm_receive_stream itself: the same instantiations, byte-identical outputs
     if (detector == OFDM_DETECT_REFERENCE && thr == OFDM_DETECT_THRESHOLD)
         return stream_receive(c, d_samples, n_samples, opts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
-                              d_counters, d_metric, d_cross, nullptr, ref);
+                              d_counters, d_metric, d_cross, nullptr, ref, dec);
     StreamDetector det{};
     det.threshold = thr;
     if (detector == OFDM_DETECT_CONJUGATE) {
@@ -253,7 +254,7 @@ int stream_receive_ex(Ctx *c, const void *d_samples, int64_t n_samples, const of
         det.name = "stream_detect_thr_kernel";
     }
     return stream_receive(c, d_samples, n_samples, opts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
-                          d_counters, d_metric, d_cross, &det, ref);
+                          d_counters, d_metric, d_cross, &det, ref, dec);
 }
 
 }  // namespace ofdm

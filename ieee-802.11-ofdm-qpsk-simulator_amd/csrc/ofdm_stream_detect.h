@@ -1,7 +1,8 @@
-// ofdm_stream_detect.h -- what ofdm_stream.hip (ofdm_receive_stream), ofdm_stream_conj.hip (ofdm_receive_stream_ex) and
-// ofdm_stream_timing.hip (ofdm_receive_stream_timed) share: the detection kernels' argument block, the hook through
-// which the extended entry point replaces the detection launch alone, and the hook through which the timed one adds a
-// launch between the selection and the decode.  The selection and decode kernels stay in ofdm_stream.hip
+// ofdm_stream_detect.h -- what ofdm_stream.hip (ofdm_receive_stream), ofdm_stream_conj.hip (ofdm_receive_stream_ex),
+// ofdm_stream_timing.hip (ofdm_receive_stream_timed) and ofdm_stream_track.hip (ofdm_receive_stream_tracked) share: the
+// detection kernels' argument block, the hook through which the extended entry point replaces the detection launch
+// alone, the hook through which the timed one adds a launch between the selection and the decode, and the hook through
+// which the tracked one replaces the decode launch.  The selection and decode kernels stay in ofdm_stream.hip
 // and are launched from there (stream_receive), so their certified builds do not move and nothing of them is restated.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -51,16 +52,38 @@ struct StreamRefiner {
     void *out;                     // the refiner's own output (optional)
 };
 
-// ofdm_receive_stream's body; det == nullptr is the reference's rule with stream_detect_kernel, and ref == nullptr no
-// launch between the selection and the decode: with both, bit for bit what the entry point enqueued before the hooks
-// existed.
+// Another decode kernel in place of stream_decode_kernel (ofdm_stream_track.hip: the pilot-tracking decode of
+// ofdm_receive_stream_tracked), under the timing id `kernel`: the launch gets the grid, the block, the dynamic LDS and
+// the argument block stream_receive has prepared for stream_decode_kernel (DecArgs, ofdm_stream_decode.h), and the
+// payload as plain MSB-first words, three per data symbol.
+struct DecArgs;
+struct StreamDecoder {
+    int kernel;                    // ofdm_timing_query id of the launch
+    void (*launch)(const StreamDecoder *dec, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const DecArgs &a,
+                   const uint32_t *payload);
+    const char *name;              // for the launch error's text
+    void *out;                     // the decoder's own output (optional)
+};
+
+// ofdm_receive_stream's body; det == nullptr is the reference's rule with stream_detect_kernel, ref == nullptr no
+// launch between the selection and the decode, and dec == nullptr stream_decode_kernel: with all three, bit for bit what
+// the entry point enqueued before the hooks existed.
 int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts, int payload,
                    int64_t max_packets, void *d_packets, void *d_count, void *d_bits, void *d_eq, void *d_counters,
-                   void *d_metric, void *d_cross, const StreamDetector *det, const StreamRefiner *ref = nullptr);
+                   void *d_metric, void *d_cross, const StreamDetector *det, const StreamRefiner *ref = nullptr,
+                   const StreamDecoder *dec = nullptr);
 
 // ofdm_receive_stream_ex's body (ofdm_stream_conj.hip): sopts checked and turned into a detector, then stream_receive
 int stream_receive_ex(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
                       const ofdm_stream_opts *sopts, int payload, int64_t max_packets, void *d_packets, void *d_count,
-                      void *d_bits, void *d_eq, void *d_counters, void *d_metric, void *d_cross, const StreamRefiner *ref);
+                      void *d_bits, void *d_eq, void *d_counters, void *d_metric, void *d_cross, const StreamRefiner *ref,
+                      const StreamDecoder *dec = nullptr);
+
+// ofdm_receive_stream_timed's body (ofdm_stream_timing.hip): timing checked and turned into a refiner, then
+// stream_receive_ex
+int stream_receive_timed(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
+                         const ofdm_stream_opts *sopts, int timing, int payload, int64_t max_packets, void *d_packets,
+                         void *d_count, void *d_bits, void *d_eq, void *d_counters, void *d_metric, void *d_cross,
+                         void *d_timing, const StreamDecoder *dec);
 
 }  // namespace ofdm

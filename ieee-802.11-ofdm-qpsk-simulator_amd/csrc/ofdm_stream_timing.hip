@@ -34,7 +34,7 @@ static_assert(TM_CAND == 64, "lane = candidate");
 static_assert(TM_FIRST == 322 && TM_FIRST + TM_WINDOW - 1 == 640, "the search window is [p + 322, p + 640]");
 static_assert(TM_WINDOW <= TM_PLANE && (TM_CAND - 1) + (TM_LEN - 1) < TM_WINDOW, "every lane's last sample is staged");
 static_assert(sizeof(ofdm_stream_timing) == 16, "ofdm_stream_timing is 16 bytes");
-static_assert(OFDM_K_STREAM_TIMING == Ctx::K_STREAM_TIMING && Ctx::K_STREAM_TIMING + 1 == Ctx::NK, "the next free timing id");
+static_assert(OFDM_K_STREAM_TIMING == Ctx::K_STREAM_TIMING && Ctx::K_STREAM_TIMING < Ctx::NK, "the timing kernel's id is one of the context's");
 
 struct TimArgs {
     const float2 *x;
@@ -178,23 +178,19 @@ static void timing_launch(const StreamRefiner *ref, Ctx *c, hipStream_t stream, 
     hipLaunchKernelGGL(stream_timing_kernel, grid, dim3(64 * TM_WAVES), 0, stream, a);
 }
 
-}  // namespace ofdm
-
-using namespace ofdm;
-
-extern "C" int ofdm_receive_stream_timed(ofdm_ctx *ctx, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
-                                         const ofdm_stream_opts *sopts, int timing, int payload, int64_t max_packets,
-                                         void *d_packets, void *d_count, void *d_bits, void *d_eq, void *d_counters,
-                                         void *d_metric, void *d_cross, void *d_timing) {
+// ofdm_receive_stream_timed's body; dec (ofdm_stream_detect.h) is handed on to stream_receive
+int stream_receive_timed(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
+                         const ofdm_stream_opts *sopts, int timing, int payload, int64_t max_packets, void *d_packets,
+                         void *d_count, void *d_bits, void *d_eq, void *d_counters, void *d_metric, void *d_cross,
+                         void *d_timing, const StreamDecoder *dec) {
     if (timing != OFDM_TIMING_NONE && timing != OFDM_TIMING_LTF && timing != OFDM_TIMING_LTF_MATLAB)
         return set_error(OFDM_E_ARG, "timing must be OFDM_TIMING_NONE (0), OFDM_TIMING_LTF (1) or OFDM_TIMING_LTF_MATLAB (2), got %d", timing);
     if (timing == OFDM_TIMING_NONE && d_timing)
         return set_error(OFDM_E_ARG, "d_timing needs OFDM_TIMING_LTF or OFDM_TIMING_LTF_MATLAB: timing is OFDM_TIMING_NONE");
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
     // no timing is ofdm_receive_stream_ex itself: the same launches, byte-identical outputs
     if (timing == OFDM_TIMING_NONE)
         return stream_receive_ex(c, d_samples, n_samples, opts, sopts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
-                                 d_counters, d_metric, d_cross, nullptr);
+                                 d_counters, d_metric, d_cross, nullptr, dec);
     StreamRefiner ref{};
     ref.kernel = OFDM_K_STREAM_TIMING;
     // the same kernel under the same id; the recording's convention only chooses the template
@@ -204,5 +200,17 @@ extern "C" int ofdm_receive_stream_timed(ofdm_ctx *ctx, const void *d_samples, i
     ref.name = "stream_timing_kernel";
     ref.out = d_timing;
     return stream_receive_ex(c, d_samples, n_samples, opts, sopts, payload, max_packets, d_packets, d_count, d_bits, d_eq,
-                             d_counters, d_metric, d_cross, &ref);
+                             d_counters, d_metric, d_cross, &ref, dec);
+}
+
+}  // namespace ofdm
+
+using namespace ofdm;
+
+extern "C" int ofdm_receive_stream_timed(ofdm_ctx *ctx, const void *d_samples, int64_t n_samples, const ofdm_rx_opts *opts,
+                                         const ofdm_stream_opts *sopts, int timing, int payload, int64_t max_packets,
+                                         void *d_packets, void *d_count, void *d_bits, void *d_eq, void *d_counters,
+                                         void *d_metric, void *d_cross, void *d_timing) {
+    return stream_receive_timed(reinterpret_cast<Ctx *>(ctx), d_samples, n_samples, opts, sopts, timing, payload, max_packets,
+                                d_packets, d_count, d_bits, d_eq, d_counters, d_metric, d_cross, d_timing, nullptr);
 }

@@ -466,7 +466,7 @@ class Engine:
                        want_bits: bool = True, want_eq: bool = False, want_metric: bool = False,
                        want_cross: bool = False, counters=None, keep_device: bool = False,
                        opts: dict | None = None, detector: str = "reference", threshold: float = 0.75,
-                       timing: str = "none") -> dict:
+                       timing: str = "none", tracking: str = "none") -> dict:
         """Every packet of one recording of any length (ofdm_receive_stream, include/ofdm_mi355x_stream.h): the
         reference's detection rule once over the whole recording, then the receiver chain on every packet found.
         opts: single fields of ofdm_rx_opts over the mode's (abi.make_rx_opts; a stream has no cap_len to set).
@@ -479,6 +479,11 @@ class Engine:
         convention decides, not mode=, which decodes either.  The result then also
         holds coarse_pos (int64 [count], front + 11), shift (int32, packet_pos - coarse_pos) and quality (float32,
         in [0, 1], 0 for a packet that was not refined) -- all three None with "none".
+        tracking: "none", or "pilots" (ofdm_receive_stream_tracked, include/ofdm_mi355x_track.h): every data symbol is
+        turned back by the common phase of its four pilots before the slicer (stream.track_pilots is the rule), and
+        records, bits and eq are those of the corrected subcarriers.  For long packets: on 2-symbol packets it costs a
+        little BER.  The result then also holds phase (float32 [count, D], radians, 0 where the rule
+        fell back to no correction) -- None with "none".
 
         samples: a one-dimensional contiguous torch complex64 tensor on this engine's device, used in place (never
         written), or a numpy complex64 array, uploaded once.  Anything else raises ValueError before any launch.
@@ -489,7 +494,8 @@ class Engine:
         messages, metric (float32 [Lc]) and cross (uint32 words, stream.unpack_cross) -- those not asked for None;
         bits, eq, metric and cross stay on the device for torch input.  The call reads the packet count back, so it
         waits for the device.  keep_device: also return d_packets (uint8 [rows, 64]), d_count (int64 [2]) and d_words
-        (int32 [rows, 3 D], None without want_bits), the device tensors the kernels wrote, for score_packets."""
+        (int32 [rows, 3 D], None without want_bits), the device tensors the kernels wrote, for score_packets, d_timing
+        and d_phase (float32 [rows, D], None without tracking)."""
         torch = _torch()
         opts = make_rx_opts(mode, opts=opts)
         nd = self.payload_frames(payload)
@@ -520,10 +526,10 @@ class Engine:
                     and counters.numel() == abi.NCOUNTERS and counters.is_contiguous()):
                 raise ValueError("counters must be a contiguous int64 device tensor of NCOUNTERS elements")
         sopts = abi.make_stream_opts(detector, threshold)
-        tcode = abi.timing_code(timing)
+        tcode, kcode = abi.timing_code(timing), abi.tracking_code(tracking)
         lc = abi.stream_positions(n, detector)
-        pk, cnt, words, eq, metric, cross, tim = self._launch_receive_stream(
-            t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross, counters, sopts, tcode)
+        pk, cnt, words, eq, metric, cross, tim, ph = self._launch_receive_stream(
+            t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross, counters, sopts, tcode, kcode)
         found, count = (int(v) for v in cnt.cpu())
         records = pk[:count].cpu().numpy().view(abi.stream_packet_dtype()).reshape(count)
         bits = None
@@ -545,23 +551,25 @@ class Engine:
             cross = None if cross is None else cross.cpu().numpy().view(np.uint32)
         out = dict(count=count, found=found, positions=records["packet_pos"].copy(), records=records, bits=bits,
                    eq=eq, messages=messages, metric=metric, cross=cross, frames=nd, coarse_pos=None, shift=None,
-                   quality=None)
+                   quality=None, phase=None)
+        if ph is not None:
+            out.update(phase=ph[:count].cpu().numpy())
         if tim is not None:
             rows = tim[:count].cpu().numpy().view(abi.stream_timing_dtype()).reshape(count)
             out.update(coarse_pos=rows["coarse_pos"].copy(), shift=rows["shift"].copy(), quality=rows["quality"].copy())
         if keep_device:
-            out.update(d_packets=pk, d_count=cnt, d_words=words, d_timing=tim)
+            out.update(d_packets=pk, d_count=cnt, d_words=words, d_timing=tim, d_phase=ph)
         return out
 
     def receive_stream_device(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
                               counters=None, detector: str = "reference", threshold: float = 0.75,
-                              timing: str = "none") -> dict:
+                              timing: str = "none", tracking: str = "none") -> dict:
         """receive_stream for a device recording without the read-back: nothing waits for the device.  samples: a
         one-dimensional contiguous torch complex64 tensor on this engine's device.  Returns d_packets (uint8
         [rows, 64], ofdm_stream_packet), d_count (int64 [2]: found, written) and d_words (int32 [rows, 3 D]), of which
         the first d_count[1] rows are written, and frames -- what score_packets takes.  detector, threshold: as
         receive_stream's.  timing: as receive_stream's; d_timing (uint8 [rows, 16], ofdm_stream_timing) with "ltf" or "ltf-matlab", else
-        None."""
+        None.  tracking: as receive_stream's; d_phase (float32 [rows, D]) with "pilots", else None."""
         torch = _torch()
         opts = make_rx_opts(mode)
         nd = self.payload_frames(payload)
@@ -579,14 +587,16 @@ class Engine:
             raise ValueError(f"max_packets must be a non-negative integer, got {max_packets!r}")
         sopts = abi.make_stream_opts(detector, threshold)
         out = self._launch_receive_stream(samples, opts, payload, nd, int(max_packets), True, False, False, False,
-                                          counters, sopts, abi.timing_code(timing))
-        return dict(d_packets=out[0], d_count=out[1], d_words=out[2], frames=nd, d_timing=out[6])
+                                          counters, sopts, abi.timing_code(timing), abi.tracking_code(tracking))
+        return dict(d_packets=out[0], d_count=out[1], d_words=out[2], frames=nd, d_timing=out[6], d_phase=out[7])
 
     def _launch_receive_stream(self, t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross,
-                               counters, sopts=None, timing=0):
-        """Allocates ofdm_receive_stream's outputs and enqueues it: (packets, count, words, eq, metric, cross, timing).
+                               counters, sopts=None, timing=0, tracking=0):
+        """Allocates ofdm_receive_stream's outputs and enqueues it: (packets, count, words, eq, metric, cross, timing,
+        phase).
         sopts (abi.StreamOpts) other than the defaults goes through ofdm_receive_stream_ex, its outputs sized by its Lc;
-        a timing other than OFDM_TIMING_NONE through ofdm_receive_stream_timed, with its rows (uint8 [rows, 16])."""
+        a timing other than OFDM_TIMING_NONE through ofdm_receive_stream_timed, with its rows (uint8 [rows, 16]); a
+        tracking other than OFDM_TRACK_NONE through ofdm_receive_stream_tracked, with its phases (float32 [rows, D])."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n = int(t.shape[0])
@@ -601,8 +611,16 @@ class Engine:
         metric = torch.empty(max(lc, 1), dtype=torch.float32, device=dev) if want_metric else None
         cross = torch.empty(max((lc + 31) // 32, 1), dtype=torch.int32, device=dev) if want_cross else None
         opt = lambda x: None if x is None else _ptr(x)
-        tim = None
-        if timing != abi.TIMING["none"]:
+        tim = ph = None
+        if tracking != abi.TRACKING["none"]:
+            if timing != abi.TIMING["none"]:
+                tim = torch.empty((rows, C.sizeof(abi.StreamTiming)), dtype=torch.uint8, device=dev)
+            ph = torch.empty((rows, nd), dtype=torch.float32, device=dev)
+            check(self.lib, self.lib.ofdm_receive_stream_tracked(
+                self.ctx, _ptr(t) if n else None, n, C.byref(opts), None if sopts is None else C.byref(sopts), timing,
+                tracking, abi.PAYLOAD[payload], max_packets, _ptr(pk), _ptr(cnt), opt(words), opt(eq), opt(counters),
+                opt(metric), opt(cross), opt(tim), _ptr(ph)), "receive_stream_tracked")
+        elif timing != abi.TIMING["none"]:
             tim = torch.empty((rows, C.sizeof(abi.StreamTiming)), dtype=torch.uint8, device=dev)
             check(self.lib, self.lib.ofdm_receive_stream_timed(
                 self.ctx, _ptr(t) if n else None, n, C.byref(opts), None if sopts is None else C.byref(sopts), timing,
@@ -616,7 +634,7 @@ class Engine:
             check(self.lib, self.lib.ofdm_receive_stream_ex(
                 self.ctx, _ptr(t) if n else None, n, C.byref(opts), C.byref(sopts), abi.PAYLOAD[payload], max_packets,
                 _ptr(pk), _ptr(cnt), opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream_ex")
-        return pk, cnt, words, eq, metric, cross, tim
+        return pk, cnt, words, eq, metric, cross, tim, ph
 
     def impair_stream(self, x, power: float, snr_db: float, cfo_hz: float = 0.0, taps=None, noise: str = "real",
                       seed: int = 0x80211A, trial: int = 0, snr_index: int = 0, index0: int = 0, lead: int = 0,

@@ -6,7 +6,9 @@ select_packets() is the executable specification of include/ofdm_mi355x_stream.h
 path.  main() is `python ofdm_pkg.py stream`.  pack_messages() packs texts into the payload words both the receivers'
 d_bits and ofdm_transmit_packets' d_words use; transmit_main() is `python ofdm_pkg.py transmit`.  score_packets() is
 the executable specification of ofdm_score_packets (include/ofdm_mi355x_channel.h).  detection_metric() and
-positions() are the executable specification of the two detectors of include/ofdm_mi355x_detect.h.
+positions() are the executable specification of the two detectors of include/ofdm_mi355x_detect.h, refine_timing() that
+of the fine timing of include/ofdm_mi355x_timing.h and track_pilots() that of the pilot phase tracking of
+include/ofdm_mi355x_track.h.
 """
 from __future__ import annotations
 
@@ -165,6 +167,51 @@ def refine_timing(x, positions, template) -> dict:
     return dict(positions=pos, coarse=coarse, shift=shift, quality=quality, metric=metric)
 
 
+TRACKINGS = ("none", "pilots")
+PILOT_BINS = (11, 25, 39, 53)             # in the reference's bin order (pilot_at, csrc/ofdm_device.h)
+PILOT_VALUES = (1.0, 1.0, 1.0, -1.0)      # OFDM.c:523
+DATA_BINS = tuple(b for b in range(6, 59) if b != 32 and b not in PILOT_BINS)    # the 48 data bins, ascending
+
+
+def track_pilots(Y, H) -> dict:
+    """The pilot phase tracking rule in double precision, the executable specification of ofdm_receive_stream_tracked
+    with OFDM_TRACK_PILOTS (include/ofdm_mi355x_track.h).  Y: the data symbols' spectra in the reference's bin order,
+    complex [D, 64] (or [64 D]: the oracle's Yf dump); H: the LS estimate, complex [64] (the oracle's H dump).
+        P_d   = sum over the pilot bins k = 11, 25, 39, 53 of p_k Y_d[k] conj(H[k]),  p = (+1, +1, +1, -1)
+        u_d   = P_d / |P_d|, or 1 when |P_d| is 0 or P_d is not finite
+        z'_d  = (Y_d[k_j] / H[k_j]) conj(u_d) over the 48 data bins k_j
+    A symbol with u_d = 1 by the fallback keeps z = Y / H as it is (a NaN included) and has phase 0.
+
+    Returns u (complex128 [D]), phase (float64 [D], the angle of P_d, radians), z (complex128 [D, 48], z'), P
+    (complex128 [D]) and fallback (bool [D])."""
+    H = np.asarray(H).astype(np.complex128).reshape(-1)
+    if len(H) != 64:
+        raise ValueError(f"an estimate of 64 bins expected, got {len(H)}")
+    Y = np.asarray(Y).astype(np.complex128)
+    if Y.size % 64:
+        raise ValueError(f"spectra of 64 bins expected, got {Y.shape}")
+    Y = Y.reshape(-1, 64)
+    pb, db = list(PILOT_BINS), list(DATA_BINS)
+    with np.errstate(all="ignore"):
+        P = (np.asarray(PILOT_VALUES) * Y[:, pb] * np.conj(H[pb])).sum(axis=1)
+        mag = np.abs(P)
+        fallback = ~(np.isfinite(P.real) & np.isfinite(P.imag) & np.isfinite(mag) & (mag > 0))
+        u = np.where(fallback, 1.0 + 0.0j, P / np.where(fallback, 1.0, mag))
+        phase = np.where(fallback, 0.0, np.angle(np.where(fallback, 1.0, P)))
+        z0 = Y[:, db] / H[db]
+        z = np.where(fallback[:, None], z0, z0 * np.conj(u)[:, None])
+    return dict(u=u, phase=phase, z=z, P=P, fallback=fallback)
+
+
+def slice_bits(z) -> np.ndarray:
+    """The C slicer and demapper (OFDM.c:852-908) on equalised subcarriers z [..., 48 D]: int32 [..., 96 D]; an axis
+    that is zero or NaN decides "-", so such a subcarrier gives the bits (1, 0)."""
+    z = np.asarray(z)
+    with np.errstate(invalid="ignore"):
+        pr, pi = z.real > 0, z.imag > 0
+    return np.stack([~pi, pr ^ pi], axis=-1).astype(np.int32).reshape(*z.shape[:-1], 2 * z.shape[-1])
+
+
 def first_packet(sel: dict) -> int:
     """Packet_Selection's answer from select_packets': the first packet that is not the last front's, 0 when none."""
     keep = sel["positions"][sel["flags"] & LAST_FRONT == 0]
@@ -309,6 +356,9 @@ def main(argv=None) -> int:
                     help="ltf: refine every packet's position against the long training field before the decode "
                          "(packets.csv then has a coarse_pos column); ltf-matlab: the same for a recording made "
                          "with the MATLAB transform convention")
+    ap.add_argument("--tracking", choices=TRACKINGS, default="none",
+                    help="pilots: turn every data symbol back by its four pilots' common phase before the slicer "
+                         "(for long packets; costs a little BER on 2-symbol packets)")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:
         raise SystemExit("--threshold must be inside (0, 1)")
@@ -331,7 +381,7 @@ def main(argv=None) -> int:
             samples = make_stream(w, synthetic_segments(len(w) // 10, a.frames, a.gap), a.snr, a.cfo_hz,
                                   taps=None if a.taps is None else parse_taps(a.taps), noise=a.noise, generator=gen)
         out = eng.receive_stream(samples, max_packets=a.max_packets, detector=a.detector, threshold=a.threshold,
-                                 timing=a.timing)
+                                 timing=a.timing, tracking=a.tracking)
     rec = out["records"]
     timed = a.timing != "none"
     d = Path(a.out)
@@ -352,6 +402,6 @@ def main(argv=None) -> int:
     return 0
 
 
-__all__ = ["ltf_template", "refine_timing", "TIMINGS", "LTF_START", "TIMING_BACK", "TIMING_FWD", "TIMING_CANDIDATES", "TIMING_FIRST", "TIMING_SPAN",
+__all__ = ["track_pilots", "slice_bits", "TRACKINGS", "PILOT_BINS", "PILOT_VALUES", "DATA_BINS", "ltf_template", "refine_timing", "TIMINGS", "LTF_START", "TIMING_BACK", "TIMING_FWD", "TIMING_CANDIDATES", "TIMING_FIRST", "TIMING_SPAN",
            "select_packets", "detection_metric", "positions", "DETECTORS", "unpack_cross", "first_packet", "synthetic_segments", "main", "pack_messages",
            "transmit_main", "score_packets", "SCORE_MAX_WINDOW", "NSCORE", "MAX_DATA_SYMBOLS", "THRESHOLD", "FRONT_GAP", "CONFIRM", "PACKET_OFFSET", "LAST_FRONT"]

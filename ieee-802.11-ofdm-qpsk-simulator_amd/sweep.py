@@ -175,7 +175,8 @@ def captures_main(argv=None):
 
 def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: float = 0.0, taps=None,
                noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=None, fading=None,
-               detector: str = "reference", threshold: float = 0.75, timing: str = "none") -> dict:
+               detector: str = "reference", threshold: float = 0.75, timing: str = "none",
+               tracking: str = "none") -> dict:
     """Packet-error and bit-error counts against SNR for packets that each carry their own bits, the recording never
     leaving the device: the packets (words: uint32 [n, 3 n_data], each behind `gap` idle samples, and a closing gap)
     are transmitted once; per SNR point q the clean recording is impaired into a second buffer with the noise stream
@@ -197,12 +198,15 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     (include/ofdm_mi355x_timing.h), which puts an unfaded packet's record at its first sample + 16.  "ltf-matlab" is accepted as well and is the same
     rule with the MATLAB convention's template; the sweep transmits C-convention packets, for which "ltf" is the
     right one.
+    tracking: "none", or "pilots": every data symbol is turned back by its four pilots' common phase before the slicer
+    (include/ofdm_mi355x_track.h).  For long packets; on 2-symbol packets it costs a little BER.
 
     Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
     import torch  # noqa: PLC0415
     snr = np.atleast_1d(np.asarray(snr_db, np.float64))
     n, plen = int(len(words)), abi.packet_len(n_data)
     abi.timing_code(timing)                                          # ValueError before anything is set or launched
+    abi.tracking_code(tracking)
     pdp = None
     if fading is not None:
         if set(fading) - {"pdp", "index0"} or "pdp" not in fading:
@@ -235,7 +239,7 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     for q, s in enumerate(snr):
         engine.impair_stream(clean, power, float(s), cfo_hz, taps=taps, noise=noise, seed=seed, trial=trial,
                              snr_index=q, out=rec)
-        rx = engine.receive_stream_device(rec, detector=detector, threshold=threshold, timing=timing)
+        rx = engine.receive_stream_device(rec, detector=detector, threshold=threshold, timing=timing, tracking=tracking)
         engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])
     return dict(snr_db=snr, totals=totals.cpu().numpy(), power=power, packets=n, samples=n_out)
 
@@ -282,6 +286,9 @@ def link_main(argv=None) -> int:
     ap.add_argument("--timing", choices=tuple(abi.TIMING), default="none",
                     help="ltf: refine every packet's position against the long training field before the decode "
                          "(ltf-matlab: with the MATLAB convention's template)")
+    ap.add_argument("--tracking", choices=tuple(abi.TRACKING), default="none",
+                    help="pilots: turn every data symbol back by its four pilots' common phase before the slicer "
+                         "(for long packets; costs a little BER on 2-symbol packets)")
     ap.add_argument("--out", default="data")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:
@@ -308,7 +315,7 @@ def link_main(argv=None) -> int:
     with Engine(0) as eng:
         res = link_sweep(eng, words, d, a.gap, snr, cfo_hz=a.cfo_hz, taps=None if a.taps is None else parse_taps(a.taps),
                          noise=a.noise, seed=a.seed, fading=fading, detector=a.detector, threshold=a.threshold,
-                         timing=a.timing)
+                         timing=a.timing, tracking=a.tracking)
     wall = time.perf_counter() - t0
     t = res["totals"]
     ber = t[:, abi.S_BIT_ERR] / np.maximum(t[:, abi.S_BITS], 1)
