@@ -78,6 +78,50 @@ int payload_table(int payload, const std::string &message, uint32_t table[3 * MS
     return frames;
 }
 
+void rrc_design(float out[21]) {
+    const double beta = 0.5, sps = 2.0, pi = M_PI;
+    double h[21], e = 0.0;
+    for (int i = 0; i < 21; ++i) {
+        const double t = (i - 10) / sps, q = 4 * beta * t;
+        double b;
+        if (t == 0.0) b = -1.0 / (pi * sps) * (pi * (beta - 1) - 4 * beta);
+        else if (std::fabs(std::fabs(q) - 1.0) < 1e-12)
+            b = 1.0 / (2 * pi * sps) * (pi * (beta + 1) * std::sin(pi * (beta + 1) / (4 * beta)) -
+                                        4 * beta * std::sin(pi * (beta - 1) / (4 * beta)) +
+                                        pi * (beta - 1) * std::cos(pi * (beta - 1) / (4 * beta)));
+        else
+            b = -4 * beta / sps * (std::cos((1 + beta) * pi * t) + std::sin((1 - beta) * pi * t) / q) / (pi * (q * q - 1));
+        h[i] = b;
+        e += b * b;
+    }
+    for (int i = 0; i < 21; ++i) out[i] = (float)(h[i] / std::sqrt(e));
+    for (int i = 0; i < 10; ++i) out[20 - i] = out[i];
+}
+
+// an axis is wrong where the truth is "+": re > 0 iff b0 == b1, im > 0 iff b0 == 0 (D10)
+uint32_t zero_errors(const uint32_t w[3]) {
+    uint32_t be = 0u, ax = 0u;
+    for (int k = 0; k < 3; ++k) be += (uint32_t)__builtin_popcount(w[k] ^ 0xAAAAAAAAu);
+    for (int m = 0; m < 48; ++m) {
+        const uint32_t b0 = (w[(2 * m) >> 5] >> (31 - ((2 * m) & 31))) & 1u;
+        const uint32_t b1 = (w[(2 * m + 1) >> 5] >> (31 - ((2 * m + 1) & 31))) & 1u;
+        ax += (uint32_t)(b0 == b1) + (uint32_t)(b0 == 0u);
+    }
+    return be | (ax << 16);
+}
+
+int wave_block(const Ctx *c, size_t head, size_t per_wave, int max_waves, int64_t items, WaveBlock *out) {
+    int lds_max = 0;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) != hipSuccess || lds_max <= 0)
+        return set_error(OFDM_E_HIP, "cannot query the device's LDS size");
+    out->limit = std::min<size_t>((size_t)lds_max, LDS_PER_CU);
+    out->W = head + per_wave > out->limit
+                 ? 0
+                 : (int)std::min<int64_t>(std::min<int64_t>(max_waves, (int64_t)((out->limit - head) / per_wave)), items);
+    out->lds = head + (size_t)std::max(out->W, 1) * per_wave;
+    return OFDM_OK;
+}
+
 int check_symbol_payload(const Ctx *c, int payload) {
     if (payload == OFDM_PAYLOAD_MESSAGE && (int)c->message.size() > MSG_MAX_CHARS)
         return set_error(OFDM_E_ARG, "symbol mode carries messages of at most %d data symbols; the message set by "

@@ -24,7 +24,22 @@ constexpr int LONG_MAX_FRAMES = OFDM_LONG_MAX_DATA_SYMBOLS;
 constexpr int LONG_MSG_MAX_CHARS = OFDM_LONG_MSG_MAX_CHARS;
 static_assert(LONG_MSG_MAX_CHARS == 12 * LONG_MAX_FRAMES, "12 characters per data symbol");
 int payload_table_long(int payload, const std::string &message, uint32_t table[3 * LONG_MAX_FRAMES]);
+// rcosdesign(0.5, 10, 2, 'sqrt') (Tester.m:112; OFDM.c:32 holds the same values as floats): the 21 RRC taps of the
+// capture and stream receivers and of the packet and fading transmitters
+void rrc_design(float out[21]);
+// The errors of a data symbol that reaches the demapper as 64 exact zeros (its window lies wholly past the end of the
+// samples; ofdm_rxchain.h rxc_totals): the reference's slicer decides "-" on both axes for a zero (Z > 0 fails,
+// OFDM.c:858-866), the demapper then (1, 0) for every pair (OFDM.c:873-908), so the counts depend on the payload alone.
+// w: the symbol's 96 payload bits, MSB first.  Returns bit errors | slicer axis errors << 16.
+uint32_t zero_errors(const uint32_t w[3]);
 struct Ctx;
+constexpr size_t LDS_PER_CU = 160 * 1024;
+// A block of one wave per item (capture, packet) in dynamic LDS: `head` bytes for the block and `per_wave` for each
+// wave, against `limit`, the smaller of the device's limit per block and LDS_PER_CU.  W = min(max_waves, what fits,
+// items) waves and their request `lds`; W = 0 when not even one wave fits (lds is then what one needs: the caller
+// words that error).  Returns non-zero (OFDM_E_HIP, the error text set) when the device cannot be asked.
+struct WaveBlock { int W; size_t lds, limit; };
+int wave_block(const Ctx *c, size_t head, size_t per_wave, int max_waves, int64_t items, WaveBlock *out);
 // OFDM_E_ARG when `payload` is MESSAGE and the message set has more than MSG_MAX_FRAMES symbols (symbol mode)
 int check_symbol_payload(const Ctx *c, int payload);
 

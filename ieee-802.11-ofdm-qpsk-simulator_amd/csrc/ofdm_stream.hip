@@ -1,9 +1,8 @@
 // ofdm_stream.hip -- the stream receiver (include/ofdm_mi355x_stream.h: ofdm_receive_stream): Packet_Detection and
 // Packet_Selection (OFDM.c:659-771) once over one device-resident recording of any length, then Receiver()'s chain
-// (OFDM.c:962-1165) on every packet found.  A translation unit of its own: ofdm_captures.hip (one capture per wave,
-// at most one packet per capture) is certified as it is, so nothing of it moves; this file shares only the inlined
-// device helpers of ofdm_rxcommon.h with it and restates capture_rx_kernel's post-selection chain (see
-// stream_decode_kernel).
+// (OFDM.c:962-1165) on every packet found.  A translation unit of its own beside ofdm_captures.hip (one capture per
+// wave, at most one packet per capture): the two share the inlined device helpers of ofdm_rxcommon.h and the
+// post-selection chain of ofdm_rxchain.h, which each kernel runs on samples it has staged its own way.
 //
 //   stream_detect_kernel<METRIC> : a block takes OFDM_STREAM_TILE positions.  It stages TILE + 47 samples once
 //     (16-byte loads, real and imaginary planes in LDS; the 47-sample halo is the only re-read), a lane owns one run
@@ -20,14 +19,14 @@
 //     2: ordered compaction -- slot order is position order -- of the first max_packets confirmed fronts into
 //     packet_pos, with the LAST_FRONT flag.  No arrival-order append anywhere: the output is deterministic.
 //   stream_decode_kernel<OUT> : one wave per packet, W waves per block, looping over d_count.  A wave stages only
-//     [p - 20, p + 2 nfr - 2] (2 nfr + 19 samples, zero outside the stream) and runs capture_rx_kernel's chain on it.
+//     [p - 20, p + 2 nfr - 2] (2 nfr + 19 samples, zero outside the stream) and runs the chain of ofdm_rxchain.h on it.
 // ofdm_receive_stream_ex (ofdm_stream_conj.hip) enters through stream_receive with a detector of its own
 // (ofdm_stream_detect.h): another detection launch, then the selection and decode launches of this file.
 // ofdm_receive_stream_timed (ofdm_stream_timing.hip) adds a refiner through the same door: one launch of its own
 // between stream_select_kernel<2> and stream_decode_kernel that rewrites packet_pos.
 // ofdm_receive_stream_tracked (ofdm_stream_track.hip) adds a decoder: its own kernel in place of stream_decode_kernel,
-// launched with the same arguments, grid and LDS.  The decode's constants, DecArgs and the sdec_ helpers live in
-// ofdm_stream_decode.h for the two decode kernels.
+// launched with the same arguments, grid and LDS.  DecArgs and the staging, filter and sync record of the two decode
+// kernels live in ofdm_stream_decode.h.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -53,8 +52,8 @@ constexpr int SS_THREADS = 256;           // slots per block of the selection ke
 constexpr int SS_SLOT = 301;              // positions per slot: fronts are at least 301 apart
 constexpr int SS_SCAN_THREADS = 1024;
 
-constexpr int SDEC_MAX_WAVES = 8;                     // 512 threads: two waves per SIMD, 256 VGPRs each
-static_assert(SDEC_MAX_WAVES == SDEC_BLOCK_WAVES, "the block stream_receive sizes fits both decode kernels' launch bounds");
+constexpr int SDEC_MAX_WAVES = 8;                     // packets per decode block at most: 512 threads, two waves per SIMD
+static_assert(SDEC_MAX_WAVES <= RXC_MAX_WAVES, "the block stream_receive sizes fits both decode kernels' launch bounds");
 static_assert(sizeof(ofdm_stream_packet) == 64, "ofdm_stream_packet is 64 bytes");
 
 // DetArgs: ofdm_stream_detect.h (shared with the detectors of ofdm_stream_conj.hip)
@@ -273,274 +272,53 @@ __global__ __launch_bounds__(PHASE == 1 ? SS_SCAN_THREADS : SS_THREADS) void str
     }
 }
 
-// The errors of a data symbol that arrives as 64 exact zeros (its window lies wholly past the stream's end), as
-// ofdm_captures.hip counts them: the reference's slicer decides "-" on both axes for a zero (OFDM.c:858-866), the
-// demapper (1, 0) for every pair, so the counts depend on the payload alone.  w: the symbol's 96 payload bits, MSB
-// first; an axis is wrong where the truth is "+": re > 0 iff b0 == b1, im > 0 iff b0 == 0 (D10).
-static uint32_t stream_zero_errors(const uint32_t w[3]) {
-    uint32_t be = 0u, ax = 0u;
-    for (int k = 0; k < 3; ++k) be += (uint32_t)__builtin_popcount(w[k] ^ 0xAAAAAAAAu);
-    for (int m = 0; m < 48; ++m) {
-        const uint32_t b0 = (w[(2 * m) >> 5] >> (31 - ((2 * m) & 31))) & 1u;
-        const uint32_t b1 = (w[(2 * m + 1) >> 5] >> (31 - ((2 * m + 1) & 31))) & 1u;
-        ax += (uint32_t)(b0 == b1) + (uint32_t)(b0 == 0u);
-    }
-    return be | (ax << 16);
-}
-
-// capture_rx_kernel's chain from the matched filter on (ofdm_captures.hip), restated here so that that kernel's
-// certified build does not move: the same filter tap order, atan2_cfo, rotation, quads, park-and-second-pass outputs
-// and counter terms, so a packet's record is what capture_rx_kernel gives for a window that contains it.  What
-// differs is the staging: the wave holds only the samples the filter reads, sample s of the stream at plane index
-// s - (p - 20), zero outside the stream, so the filter needs no bounds test.
+// One wave per packet: ofdm_stream_decode.h's staging, filter and sync record, then ofdm_rxchain.h's stages -- the chain
+// capture_rx_kernel runs from the matched filter on, so a packet's record is what that kernel gives for a window that
+// contains it.
 template <bool OUT>   // OUT: d_bits and / or d_eq are written
-__global__ __launch_bounds__(64 * SDEC_MAX_WAVES) void stream_decode_kernel(DecArgs a) {
+__global__ __launch_bounds__(64 * RXC_MAX_WAVES) void stream_decode_kernel(DecArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long sdec_smem[];
     unsigned long long *acc = sdec_smem;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), W = blockDim.x >> 6;
     const int nd = a.n_data, nfr = 320 + 80 * nd, plane = a.plane, len = 2 * nfr + 19;
-    float *re = reinterpret_cast<float *>(sdec_smem + SDEC_ACC_WORDS) + (size_t)wave * a.wave_floats;
+    float *re = reinterpret_cast<float *>(sdec_smem + RXC_ACC_WORDS) + (size_t)wave * a.wave_floats;
     float *im = re + plane;
     float *fre = re + 2 * plane, *fim = fre + nfr;
-    if (threadIdx.x < SDEC_ACC_WORDS) acc[threadIdx.x] = 0ull;
+    if (threadIdx.x < RXC_ACC_WORDS) acc[threadIdx.x] = 0ull;
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int64_t cnt = a.count[1];
     const int q = (int)((reinterpret_cast<uintptr_t>(a.x) >> 3) & 1u);     // sample s is 16-byte aligned when s + q is even
     for (int64_t i = (int64_t)blockIdx.x * W + wave; i < cnt; i += (int64_t)gridDim.x * W) {
         ofdm_stream_packet *pkt = a.pk + i;
-        const int64_t pv = pkt->packet_pos;
-        const int64_t p = ((int64_t)__builtin_amdgcn_readfirstlane((int)(pv >> 32)) << 32) |
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)pv);
-        const int last_front = __builtin_amdgcn_readfirstlane(pkt->r.flags) & OFDM_STREAM_LAST_FRONT;
-        // ---- stage [p - 20, p + 2 nfr - 2]: aligned 16-byte loads inside the stream, zero outside ----
-        {
-            const int64_t s0 = p - 20, e0 = s0 - ((s0 + q) & 1);
-            for (int kb = lane; 2 * kb < len + 1; kb += 64 * SDEC_LOADS) {     // SDEC_LOADS loads in flight, then their writes
-                f4v t[SDEC_LOADS];
-#pragma unroll
-                for (int j = 0; j < SDEC_LOADS; ++j) {
-                    const int k = kb + 64 * j;
-                    const int64_t s = e0 + 2 * k;
-                    t[j] = f4v{0.f, 0.f, 0.f, 0.f};
-                    if (2 * k >= len + 1) continue;
-                    if (s >= 0 && s + 1 < a.n) {
-                        t[j] = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(a.x + s));
-                    } else {
-                        if (s >= 0 && s < a.n) { const float2 u = a.x[s]; t[j].x = u.x; t[j].y = u.y; }
-                        if (s + 1 >= 0 && s + 1 < a.n) { const float2 u = a.x[s + 1]; t[j].z = u.x; t[j].w = u.y; }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < SDEC_LOADS; ++j) {
-                    const int k = kb + 64 * j;
-                    const int m = 2 * k - (int)(s0 - e0);                  // -1 for the pair's first sample when e0 < s0
-                    if (2 * k >= len + 1) continue;
-                    if (m >= 0 && m < len) { re[m] = t[j].x; im[m] = t[j].y; }
-                    if (m + 1 < len) { re[m + 1] = t[j].z; im[m + 1] = t[j].w; }
-                }
-            }
-        }
-        sdec_wave_sync();
-        // ---- RRC matched filter at the down-sampled instants: stream sample p + 2 ii - tt is plane index 20 + 2 ii - tt ----
+        int64_t p;
+        int last_front;
+        sdec_packet(pkt, p, last_front);
+        sdec_stage(a.x, a.n, p, q, len, lane, re, im);
+        rxc_wave_sync();
         const bool oob = p + 2 * (int64_t)(nfr - 1) >= a.n + 20;       // the reference reads past its buffer
         // the first data symbol wholly past the end: the least d >= 0 with p + 2 (336 + 80 d) >= n + 20; D when none
         const int zfirst = (int)std::min<int64_t>(std::max<int64_t>((a.n - 652 - p + 159) / 160, 0), nd);
-        for (int ii = lane; ii < nfr; ii += 64) {
-            if (!sdec_needed(ii)) continue;
-            const int n = 20 + 2 * ii;
-            float vx = 0.f, vy = 0.f;
-#pragma unroll
-            for (int tt = 0; tt < 21; ++tt) {
-                vx = fmaf(re[n - tt], a.taps[tt], vx);
-                vy = fmaf(im[n - tt], a.taps[tt], vy);
-            }
-            fre[ii] = vx;
-            fim[ii] = vy;
-        }
-        sdec_wave_sync();
-        // ---- Coarse_CFO_Estimation, Fine_CFO_Estimation (OFDM.c:773-828) ----
+        sdec_filter(re, im, a.taps, nfr, lane, fre, fim);
+        rxc_wave_sync();
         double fc, ff;
-        {
-            const int k = lane & 15;
-            const float2 cu = make_float2(fre[80 + k], fim[80 + k]), cw = make_float2(fre[96 + k], fim[96 + k]);
-            float2 pp = lane < 16 ? cmulc(cu, cw) : make_float2(0.f, 0.f);
-            pp.x = sdec_sum_f(pp.x);
-            pp.y = sdec_sum_f(pp.y);
-            fc = (-1.0 / (2.0 * M_PI * 16.0 * SDEC_TS)) * (double)atan2_cfo(pp.y, pp.x);
-            if (a.float_cfo) fc = (double)(float)fc;
-            const float2 u = sdec_rot(make_float2(fre[192 + lane], fim[192 + lane]), fc * SDEC_TS, 192 + lane);
-            const float2 w = sdec_rot(make_float2(fre[256 + lane], fim[256 + lane]), fc * SDEC_TS, 256 + lane);
-            pp = cmulc(u, w);
-            pp.x = sdec_sum_f(pp.x);
-            pp.y = sdec_sum_f(pp.y);
-            ff = (-1.0 / (2.0 * M_PI * 64.0 * SDEC_TS)) * (double)atan2_cfo(pp.y, pp.x);
-            if (a.float_cfo) ff = (double)(float)ff;
-        }
-        // the sync half of the record and its counter term leave here, so nothing of it stays live over the transforms
-        if (lane == 0) {
-            ofdm_capture_result *r = &pkt->r;
-            r->packet_idx = p <= 0x7fffffffll ? (int32_t)p : -1;
-            r->flags = last_front | (oob ? OFDM_CAPTURE_OOB : 0);
-            r->cfo_coarse_hz = (float)fc;
-            r->cfo_fine_hz = (float)ff;
-            r->reserved[0] = 0;
-            r->reserved[1] = 0;
-            if (a.counters) atomicAdd(&acc[OFDM_C_OOB], (unsigned long long)oob);
-        }
-        // ---- the combined rotation in place, 64 samples per step: the LTF pair's sum over LTF1, then the data windows ----
-        {
-            const double fcf_ts = (fc + ff) * SDEC_TS;
-            const int k = 192 + lane;
-            const float2 u = sdec_rot(make_float2(fre[k], fim[k]), fcf_ts, k);
-            const float2 w = sdec_rot(make_float2(fre[k + 64], fim[k + 64]), fcf_ts, k + 64);
-            fre[k] = u.x + w.x;
-            fim[k] = u.y + w.y;
-            for (int d = 0; d < nd; ++d) {
-                const int kd = 336 + 80 * d + lane;
-                const float2 v = sdec_rot(make_float2(fre[kd], fim[kd]), fcf_ts, kd);
-                fre[kd] = v.x;
-                fim[kd] = v.y;
-            }
-        }
-        sdec_wave_sync();
-        // ---- symbols: quad {LTF1 + LTF2, D_3q, D_3q+1, D_3q+2}; fft() = DFT(x (-1)^n) ----
-        const int role = lane & 3, dsym = 3 * (lane >> 2) + max(role - 1, 0), dsc = min(dsym, nd - 1);
-        const bool dlane = role >= 1 && dsym < nd;
-        const int k0 = role == 0 ? 192 : 336 + 80 * dsc;
+        rxc_cfo(fre, fim, lane, a.float_cfo, fc, ff);
+        sdec_sync_record(&pkt->r, acc, a.counters != nullptr, lane, p, last_front, oob, fc, ff);
+        rxc_rotate(fre, fim, lane, nd, fc, ff);
+        rxc_wave_sync();
+        const RxcQuad qd = rxc_quad(lane, nd);
         float2 x[64];
-        static_for<0, 64>([&](auto nc) {
-            constexpr int n = decltype(nc)::value;
-            const float vx = fre[k0 + n], vy = fim[k0 + n];
-            x[n] = (n & 1) ? make_float2(-vx, -vy) : make_float2(vx, vy);
-        });
-        static_for<0, 16>([&](auto jc) { dif_stage1<false, decltype(jc)::value>(x); });
-        const uint32_t wd[4] = {a.dtable[4 * dsc], a.dtable[4 * dsc + 1], a.dtable[4 * dsc + 2], a.dtable[4 * dsc + 3]};
+        rxc_window(fre, fim, qd.k0, x);
         SymState st;
-        sym_init(st);
-        auto Hof = [&](float2 Y, auto binc) { return ls_equalise<decltype(binc)::value>(Y); };
-        // OUT: every window is in registers by now, so the wave's region is free: the quads in use park their finished
-        // spectra there for the output pass below (no branch around the writes: the idle lanes share one more row)
-        [[maybe_unused]] float2 *spec_row = reinterpret_cast<float2 *>(re + min(lane, 4 * ((nd + 2) / 3)) * SDEC_SPEC_PITCH);
-        if constexpr (OUT) sdec_wave_sync();
-        static_for<0, 4>([&](auto rc) {
-            constexpr int R = decltype(rc)::value;
-            dif_sub16<false, R>(x);
-            demap_sub<false, R, 2>(x, wd[R], Hof, nullptr, st);
-            sched_fence();
-            if constexpr (OUT) {
-                static_for<0, 16>([&](auto kc) {
-                    constexpr int bin = 4 * decltype(kc)::value + R;
-                    spec_row[bin] = x[digit_rev4(bin)];
-                });
-                sched_fence();
-            }
-        });
-        // OUT: the equalised subcarriers Z = Y / H = 2 Lf Y conj(S) / |S|^2 and the decided bits (OFDM.c:1044-1052,
-        // 852-908), one subcarrier per lane and step: coalesced stores, a 16-lane OR per word of 32 bits
-        if constexpr (OUT) {
-            sdec_wave_sync();
-            const int nsc = 48 * nd;
-            for (int j0 = 0; j0 < nsc; j0 += 64) {
-                const int j = j0 + lane;
-                const bool ok = j < nsc;
-                const int jj = ok ? j : 0, d = jj / 48, m = jj - 48 * d, bin = data_bin(m);
-                const int l0 = 4 * (d / 3), ln = l0 + 1 + d % 3;
-                const float2 Y = reinterpret_cast<const float2 *>(re + ln * SDEC_SPEC_PITCH)[bin];
-                const float2 S = reinterpret_cast<const float2 *>(re + l0 * SDEC_SPEC_PITCH)[bin];
-                const float r = __builtin_amdgcn_rcpf(fmaf(S.x, S.x, S.y * S.y));
-                const float g = ((SDEC_LTF_NEG >> bin) & 1ull) ? -2.0f * r : 2.0f * r;
-                const float2 u = cmulc(Y, S);
-                const float2 z = make_float2(u.x * g, u.y * g);
-                if (a.eq && ok) a.eq[i * nsc + j] = z;
-                const uint32_t pr = z.x > 0.f, pi = z.y > 0.f;
-                uint32_t wv = ok ? (((pi ^ 1u) << 1) | (pr ^ pi)) << (30 - 2 * (lane & 15)) : 0u;
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) wv |= (uint32_t)__shfl_xor((int)wv, o, 64);
-                if (a.bits && ok && (lane & 15) == 0) a.bits[i * (3 * nd) + (j >> 4)] = wv;
-            }
-        }
-        // ---- the packet's totals in symbol order, its record and its counter terms ----
-        // A data symbol whose window lies wholly past the stream's end reached the demapper as 64 exact zeros, where the
-        // sign bit of u = +-0 that demap_sub counts is an accident of S; the reference decides "-" on both axes for a zero,
-        // as the output pass above does, so that symbol's counts are the payload's own (ztable; capture_rx_kernel's rule:
-        // symbols zfirst .. D - 1, a wave-uniform, rare branch after the transforms).  Its EVM term needs nothing: u' =
-        // +-0 gives |0 - d|^2 either way.
-        const float fev = dlane ? finish_evm<2>(st) : 0.f;
-        const uint32_t bev = dlane ? st.be : 0u, axv = dlane ? st.ax : 0u;
-        float fe = 0.f;
-        uint32_t ferr = 0u, fax = 0u;
-        for (int d = 0; d < nd; ++d) {
-            const int src = 4 * (d / 3) + 1 + d % 3;
-            fe += __shfl(fev, src, 64);
-            ferr += (uint32_t)__shfl((int)bev, src, 64);
-            fax += (uint32_t)__shfl((int)axv, src, 64);
-        }
-        if (zfirst < nd) {
-            for (int d = zfirst; d < nd; ++d) {
-                const int src = 4 * (d / 3) + 1 + d % 3;
-                const uint32_t z = a.ztable[d];
-                ferr += (z & 0xffffu) - (uint32_t)__shfl((int)bev, src, 64);
-                fax += (z >> 16) - (uint32_t)__shfl((int)axv, src, 64);
-            }
-        }
-        if (lane == 0) {
-            const float N = 48.0f * (float)nd;
-            // a NaN sum (the stream ends before the long training symbols: S = 0, Z = 0 / 0) stays NaN, as the reference's
-            const float db = fe > 0.f ? fmaxf(3.01029995663981195214f * __builtin_amdgcn_logf(fe / N), -400.f)
-                                      : (fe == fe ? -400.f : fe);
-            const float dbp = fax > 0u ? 3.01029995663981195214f * __builtin_amdgcn_logf(2.0f * (float)fax / N) : -INFINITY;
-            ofdm_capture_result *r = &pkt->r;
-            r->bit_err = (int32_t)ferr;
-            r->post_axis_err = (int32_t)fax;
-            r->evm_pre_sum = fe;
-            r->evm_db_pre = db;
-            r->evm_db_post = dbp;
-            r->ber = (float)ferr / (96.0f * (float)nd);
-            if (a.counters) {
-                const float Q = (float)OFDM_EVM_Q_SCALE;             // x 2^20 is exact in fp32
-                atomicAdd(&acc[OFDM_C_FRAMES], 1ull);
-                atomicAdd(&acc[OFDM_C_SYMBOLS], (unsigned long long)nd);
-                atomicAdd(&acc[OFDM_C_BITS], 96ull * nd);
-                atomicAdd(&acc[OFDM_C_EVM_TERMS], 48ull * nd);
-                atomicAdd(&acc[OFDM_C_BIT_ERR], (unsigned long long)ferr);
-                atomicAdd(&acc[OFDM_C_FRAME_ERR], (unsigned long long)(ferr > 0u));
-                atomicAdd(&acc[OFDM_C_EVM_POST_AXIS], (unsigned long long)fax);
-                if (fabsf(fe) < INFINITY) {                          // a non-finite term is left out, never converted
-                    atomicAdd(&acc[OFDM_C_EVM_PRE_Q], (unsigned long long)__float2ll_rn(fe * Q));
-                    atomicAdd(&acc[OFDM_C_EVMDB_PRE_Q], (unsigned long long)__float2ll_rn(db * Q));
-                }
-                if (fax > 0u) {
-                    atomicAdd(&acc[OFDM_C_EVMDB_POST_Q], (unsigned long long)__float2ll_rn(dbp * Q));
-                    atomicAdd(&acc[OFDM_C_EVMDB_POST_FINITE], 1ull);
-                }
-            }
-        }
-        sdec_wave_sync();                                            // the next packet overwrites the planes
+        rxc_demap<OUT>(x, a.dtable, qd.dsc, re, lane, nd, st);
+        if constexpr (OUT) rxc_outputs(re, lane, nd, i, a.eq, a.bits);
+        float fe;
+        uint32_t ferr, fax;
+        rxc_totals(st, qd.dlane, nd, zfirst, a.ztable, fe, ferr, fax);
+        rxc_record(&pkt->r, acc, a.counters != nullptr, lane, nd, fe, ferr, fax);
+        rxc_wave_sync();                                             // the next packet overwrites the planes
     }
-    __syncthreads();
-    if (a.counters && threadIdx.x < SDEC_ACC_WORDS && acc[threadIdx.x]) atomicAdd(&a.counters[threadIdx.x], acc[threadIdx.x]);
-}
-
-// rcosdesign(0.5, 10, 2, 'sqrt') (Tester.m:112; OFDM.c:32 holds the same values as floats), as ofdm_captures.hip
-static void stream_taps(float out[21]) {
-    const double beta = 0.5, sps = 2.0, pi = M_PI;
-    double h[21], e = 0.0;
-    for (int i = 0; i < 21; ++i) {
-        const double t = (i - 10) / sps, q = 4 * beta * t;
-        double b;
-        if (t == 0.0) b = -1.0 / (pi * sps) * (pi * (beta - 1) - 4 * beta);
-        else if (std::fabs(std::fabs(q) - 1.0) < 1e-12)
-            b = 1.0 / (2 * pi * sps) * (pi * (beta + 1) * std::sin(pi * (beta + 1) / (4 * beta)) -
-                                        4 * beta * std::sin(pi * (beta - 1) / (4 * beta)) +
-                                        pi * (beta - 1) * std::cos(pi * (beta - 1) / (4 * beta)));
-        else
-            b = -4 * beta / sps * (std::cos((1 + beta) * pi * t) + std::sin((1 - beta) * pi * t) / q) / (pi * (q * q - 1));
-        h[i] = b;
-        e += b * b;
-    }
-    for (int i = 0; i < 21; ++i) out[i] = (float)(h[i] / std::sqrt(e));
-    for (int i = 0; i < 10; ++i) out[20 - i] = out[i];
+    rxc_flush(acc, a.counters);
 }
 
 // ofdm_receive_stream's body.  det (ofdm_stream_detect.h): another detection launch in place of stream_detect_kernel,
@@ -572,25 +350,21 @@ int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_
     da.n_data = payload_table_long(payload, c->message, table);
     for (int d = 0; d < da.n_data; ++d) {
         demap_words(table + 3 * d, da.dtable + 4 * d);
-        da.ztable[d] = stream_zero_errors(table + 3 * d);
+        da.ztable[d] = zero_errors(table + 3 * d);
     }
     const int nfr = 320 + 80 * da.n_data;
     // the decode block's LDS, checked before anything is launched
     da.plane = (2 * nfr + 19 + 3) & ~3;
-    const int spec_floats = (4 * ((da.n_data + 2) / 3) + 1) * SDEC_SPEC_PITCH;
-    da.wave_floats = (std::max(2 * da.plane + 2 * nfr, spec_floats) + 3) & ~3;
-    int lds_max = 0;
-    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) != hipSuccess || lds_max <= 0)
-        return set_error(OFDM_E_HIP, "cannot query the device's LDS size");
-    const size_t limit = std::min<size_t>((size_t)lds_max, SDEC_LDS_PER_CU);
-    const size_t head = SDEC_ACC_WORDS * sizeof(unsigned long long), per_wave = (size_t)da.wave_floats * sizeof(float);
-    if (head + per_wave > limit)
+    da.wave_floats = (std::max(2 * da.plane + 2 * nfr, rxc_spec_floats(da.n_data)) + 3) & ~3;
+    WaveBlock wb;
+    if (wave_block(c, RXC_ACC_WORDS * sizeof(unsigned long long), (size_t)da.wave_floats * sizeof(float), SDEC_MAX_WAVES,
+                   std::max<int64_t>(max_packets, 1), &wb))
+        return OFDM_E_HIP;
+    if (!wb.W)
         return set_error(OFDM_E_ARG, "a %d-symbol packet needs %zu bytes of LDS, above the %zu available", da.n_data,
-                         head + per_wave, limit);
-    const int W = (int)std::min<int64_t>(std::min<int64_t>(SDEC_MAX_WAVES, (int64_t)((limit - head) / per_wave)),
-                                         std::max<int64_t>(max_packets, 1));
-    const size_t lds = head + (size_t)W * per_wave;
-    if (lds > limit) return set_error(OFDM_E_ARG, "dynamic LDS request %zu above the limit %zu", lds, limit);
+                         wb.lds, wb.limit);
+    const int W = wb.W;
+    const size_t lds = wb.lds;
 
     // scratch: the crossing bitmap (whole 16-byte groups), the front slots, the selection blocks' counts and maxima
     const int64_t lc = n_samples - halo;
@@ -667,7 +441,7 @@ int stream_receive(Ctx *c, const void *d_samples, int64_t n_samples, const ofdm_
     da.eq = (float2 *)d_eq;
     da.counters = (unsigned long long *)d_counters;
     da.float_cfo = opts->float_cfo;
-    stream_taps(da.taps);
+    rrc_design(da.taps);
     // the packet count stays on the device: enough blocks for max_packets, at most two per CU; the waves loop over d_count
     const int64_t blocks = (max_packets + W - 1) / W;
     const dim3 grid((unsigned)std::min<int64_t>(blocks, 2 * (int64_t)c->cus));

@@ -2,8 +2,8 @@
 // ofdm_stream_timing.hip (ofdm_receive_stream_timed) and ofdm_stream_track.hip (ofdm_receive_stream_tracked) share: the
 // detection kernels' argument block, the hook through which the extended entry point replaces the detection launch
 // alone, the hook through which the timed one adds a launch between the selection and the decode, and the hook through
-// which the tracked one replaces the decode launch.  The selection and decode kernels stay in ofdm_stream.hip
-// and are launched from there (stream_receive), so their certified builds do not move and nothing of them is restated.
+// which the tracked one replaces the decode launch.  The selection and decode kernels stay in ofdm_stream.hip and are
+// launched from there (stream_receive); the decode kernels' chain itself is ofdm_stream_decode.h and ofdm_rxchain.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -5,9 +5,10 @@
 // and dynamic LDS.
 //
 //   stream_decode_track_kernel : one wave per packet, W waves per block, looping over d_count, as stream_decode_kernel.
-//     Through the quads' transforms the chain is that kernel's, restated here so that its certified build does not
-//     move (the precedent: ofdm_captures.hip -> ofdm_stream.hip): staging, the matched filter at the used instants,
-//     coarse and fine CFO, the combined rotation, quads {LTF1 + LTF2, D_3q, D_3q+1, D_3q+2}.  From there:
+//     Through the transforms' first stage the chain is that kernel's, from the same inlined stages (ofdm_stream_decode.h:
+//     staging, the matched filter at the used instants, the sync record; ofdm_rxchain.h: coarse and fine CFO, the
+//     combined rotation, quads {LTF1 + LTF2, D_3q, D_3q+1, D_3q+2}, the window load), and so is the record's decode
+//     half and the counter terms from the packet's totals.  In between:
 //       1  every lane parks its finished spectrum in the wave's LDS region (row pitch 130 floats: the 64 lanes' 8-byte
 //          writes of one bin fall on distinct bank pairs) -- nothing is demapped inside the transform, since the pilot
 //          bins 11 and 39 finish in sub-transform 3 and 25 and 53 in sub-transform 1, after most data bins;
@@ -31,7 +32,7 @@ namespace ofdm {
 
 static_assert(OFDM_K_STREAM_DECODE_TRACK == Ctx::K_STREAM_DECODE_TRACK && Ctx::K_STREAM_DECODE_TRACK < Ctx::NK,
               "the tracking decode's id is one of the context's");
-static_assert(4 * SDEC_MAX_DATA <= 64, "the pilot step is one step: lane 4 d + i");
+static_assert(4 * RXC_MAX_DATA <= 64, "the pilot step is one step: lane 4 d + i");
 
 struct TrackArgs {
     const float2 *x;
@@ -46,7 +47,7 @@ struct TrackArgs {
     int32_t plane;           // floats per plane (2 nfr + 19 rounded up to 4)
     int32_t wave_floats;     // floats per wave: two planes and fr[]
     float taps[21];
-    uint32_t words[3 * SDEC_MAX_DATA];   // the payload, MSB first, three words per data symbol
+    uint32_t words[3 * RXC_MAX_DATA];   // the payload, MSB first, three words per data symbol
 };
 
 // the pilots' bins (pilot_at, ofdm_device.h) and p_k L_k
@@ -59,140 +60,48 @@ constexpr uint32_t track_pilot_neg() {
 }
 constexpr uint32_t TRACK_PILOT_NEG = track_pilot_neg();
 
-__global__ __launch_bounds__(64 * SDEC_BLOCK_WAVES) void stream_decode_track_kernel(TrackArgs a) {
+__global__ __launch_bounds__(64 * RXC_MAX_WAVES) void stream_decode_track_kernel(TrackArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long strk_smem[];
     unsigned long long *acc = strk_smem;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), W = blockDim.x >> 6;
     const int nd = a.n_data, nfr = 320 + 80 * nd, plane = a.plane, len = 2 * nfr + 19;
-    float *re = reinterpret_cast<float *>(strk_smem + SDEC_ACC_WORDS) + (size_t)wave * a.wave_floats;
+    float *re = reinterpret_cast<float *>(strk_smem + RXC_ACC_WORDS) + (size_t)wave * a.wave_floats;
     float *im = re + plane;
     float *fre = re + 2 * plane, *fim = fre + nfr;
-    if (threadIdx.x < SDEC_ACC_WORDS) acc[threadIdx.x] = 0ull;
+    if (threadIdx.x < RXC_ACC_WORDS) acc[threadIdx.x] = 0ull;
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int64_t cnt = a.count[1];
     const int q = (int)((reinterpret_cast<uintptr_t>(a.x) >> 3) & 1u);     // sample s is 16-byte aligned when s + q is even
     for (int64_t i = (int64_t)blockIdx.x * W + wave; i < cnt; i += (int64_t)gridDim.x * W) {
         ofdm_stream_packet *pkt = a.pk + i;
-        const int64_t pv = pkt->packet_pos;
-        const int64_t p = ((int64_t)__builtin_amdgcn_readfirstlane((int)(pv >> 32)) << 32) |
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)pv);
-        const int last_front = __builtin_amdgcn_readfirstlane(pkt->r.flags) & OFDM_STREAM_LAST_FRONT;
-        // ---- stage [p - 20, p + 2 nfr - 2]: aligned 16-byte loads inside the stream, zero outside ----
-        {
-            const int64_t s0 = p - 20, e0 = s0 - ((s0 + q) & 1);
-            for (int kb = lane; 2 * kb < len + 1; kb += 64 * SDEC_LOADS) {     // SDEC_LOADS loads in flight, then their writes
-                f4v t[SDEC_LOADS];
-#pragma unroll
-                for (int j = 0; j < SDEC_LOADS; ++j) {
-                    const int k = kb + 64 * j;
-                    const int64_t s = e0 + 2 * k;
-                    t[j] = f4v{0.f, 0.f, 0.f, 0.f};
-                    if (2 * k >= len + 1) continue;
-                    if (s >= 0 && s + 1 < a.n) {
-                        t[j] = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(a.x + s));
-                    } else {
-                        if (s >= 0 && s < a.n) { const float2 u = a.x[s]; t[j].x = u.x; t[j].y = u.y; }
-                        if (s + 1 >= 0 && s + 1 < a.n) { const float2 u = a.x[s + 1]; t[j].z = u.x; t[j].w = u.y; }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < SDEC_LOADS; ++j) {
-                    const int k = kb + 64 * j;
-                    const int m = 2 * k - (int)(s0 - e0);                  // -1 for the pair's first sample when e0 < s0
-                    if (2 * k >= len + 1) continue;
-                    if (m >= 0 && m < len) { re[m] = t[j].x; im[m] = t[j].y; }
-                    if (m + 1 < len) { re[m + 1] = t[j].z; im[m + 1] = t[j].w; }
-                }
-            }
-        }
-        sdec_wave_sync();
-        // ---- RRC matched filter at the down-sampled instants: stream sample p + 2 ii - tt is plane index 20 + 2 ii - tt ----
+        int64_t p;
+        int last_front;
+        sdec_packet(pkt, p, last_front);
+        sdec_stage(a.x, a.n, p, q, len, lane, re, im);
+        rxc_wave_sync();
         const bool oob = p + 2 * (int64_t)(nfr - 1) >= a.n + 20;       // the reference reads past its buffer
-        for (int ii = lane; ii < nfr; ii += 64) {
-            if (!sdec_needed(ii)) continue;
-            const int n = 20 + 2 * ii;
-            float vx = 0.f, vy = 0.f;
-#pragma unroll
-            for (int tt = 0; tt < 21; ++tt) {
-                vx = fmaf(re[n - tt], a.taps[tt], vx);
-                vy = fmaf(im[n - tt], a.taps[tt], vy);
-            }
-            fre[ii] = vx;
-            fim[ii] = vy;
-        }
-        sdec_wave_sync();
-        // ---- Coarse_CFO_Estimation, Fine_CFO_Estimation (OFDM.c:773-828) ----
+        sdec_filter(re, im, a.taps, nfr, lane, fre, fim);
+        rxc_wave_sync();
         double fc, ff;
+        rxc_cfo(fre, fim, lane, a.float_cfo, fc, ff);
+        sdec_sync_record(&pkt->r, acc, a.counters != nullptr, lane, p, last_front, oob, fc, ff);
+        rxc_rotate(fre, fim, lane, nd, fc, ff);
+        rxc_wave_sync();
+        // ---- the quads' transforms: nothing is demapped inside them, every lane parks its finished spectrum ----
         {
-            const int k = lane & 15;
-            const float2 cu = make_float2(fre[80 + k], fim[80 + k]), cw = make_float2(fre[96 + k], fim[96 + k]);
-            float2 pp = lane < 16 ? cmulc(cu, cw) : make_float2(0.f, 0.f);
-            pp.x = sdec_sum_f(pp.x);
-            pp.y = sdec_sum_f(pp.y);
-            fc = (-1.0 / (2.0 * M_PI * 16.0 * SDEC_TS)) * (double)atan2_cfo(pp.y, pp.x);
-            if (a.float_cfo) fc = (double)(float)fc;
-            const float2 u = sdec_rot(make_float2(fre[192 + lane], fim[192 + lane]), fc * SDEC_TS, 192 + lane);
-            const float2 w = sdec_rot(make_float2(fre[256 + lane], fim[256 + lane]), fc * SDEC_TS, 256 + lane);
-            pp = cmulc(u, w);
-            pp.x = sdec_sum_f(pp.x);
-            pp.y = sdec_sum_f(pp.y);
-            ff = (-1.0 / (2.0 * M_PI * 64.0 * SDEC_TS)) * (double)atan2_cfo(pp.y, pp.x);
-            if (a.float_cfo) ff = (double)(float)ff;
-        }
-        // the sync half of the record and its counter term leave here, so nothing of it stays live over the transforms
-        if (lane == 0) {
-            ofdm_capture_result *r = &pkt->r;
-            r->packet_idx = p <= 0x7fffffffll ? (int32_t)p : -1;
-            r->flags = last_front | (oob ? OFDM_CAPTURE_OOB : 0);
-            r->cfo_coarse_hz = (float)fc;
-            r->cfo_fine_hz = (float)ff;
-            r->reserved[0] = 0;
-            r->reserved[1] = 0;
-            if (a.counters) atomicAdd(&acc[OFDM_C_OOB], (unsigned long long)oob);
-        }
-        // ---- the combined rotation in place, 64 samples per step: the LTF pair's sum over LTF1, then the data windows ----
-        {
-            const double fcf_ts = (fc + ff) * SDEC_TS;
-            const int k = 192 + lane;
-            const float2 u = sdec_rot(make_float2(fre[k], fim[k]), fcf_ts, k);
-            const float2 w = sdec_rot(make_float2(fre[k + 64], fim[k + 64]), fcf_ts, k + 64);
-            fre[k] = u.x + w.x;
-            fim[k] = u.y + w.y;
-            for (int d = 0; d < nd; ++d) {
-                const int kd = 336 + 80 * d + lane;
-                const float2 v = sdec_rot(make_float2(fre[kd], fim[kd]), fcf_ts, kd);
-                fre[kd] = v.x;
-                fim[kd] = v.y;
-            }
-        }
-        sdec_wave_sync();
-        // ---- symbols: quad {LTF1 + LTF2, D_3q, D_3q+1, D_3q+2}; fft() = DFT(x (-1)^n) ----
-        {
-            const int role = lane & 3, dsym = 3 * (lane >> 2) + max(role - 1, 0), dsc = min(dsym, nd - 1);
-            const int k0 = role == 0 ? 192 : 336 + 80 * dsc;
             float2 x[64];
-            static_for<0, 64>([&](auto nc) {
-                constexpr int n = decltype(nc)::value;
-                const float vx = fre[k0 + n], vy = fim[k0 + n];
-                x[n] = (n & 1) ? make_float2(-vx, -vy) : make_float2(vx, vy);
-            });
-            static_for<0, 16>([&](auto jc) { dif_stage1<false, decltype(jc)::value>(x); });
-            // every window is in registers by now, so the wave's region is free: the quads in use park their finished
-            // spectra there (no branch around the writes: the idle lanes share one more row)
-            float2 *spec_row = reinterpret_cast<float2 *>(re + min(lane, 4 * ((nd + 2) / 3)) * SDEC_SPEC_PITCH);
-            sdec_wave_sync();
+            rxc_window(fre, fim, rxc_quad(lane, nd).k0, x);
+            float2 *spec_row = rxc_spec_row(re, lane, nd);
+            rxc_wave_sync();
             static_for<0, 4>([&](auto rc) {
                 constexpr int R = decltype(rc)::value;
                 dif_sub16<false, R>(x);
-                static_for<0, 16>([&](auto kc) {
-                    constexpr int bin = 4 * decltype(kc)::value + R;
-                    spec_row[bin] = x[digit_rev4(bin)];
-                });
+                rxc_park<R>(x, spec_row);
                 sched_fence();
             });
         }
-        sdec_wave_sync();
+        rxc_wave_sync();
         // ---- the pilot step: lane 4 d + i is term i of P_d; every lane of the four ends with u_d ----
         float ux = 1.f, uy = 0.f;
         {
@@ -200,8 +109,8 @@ __global__ __launch_bounds__(64 * SDEC_BLOCK_WAVES) void stream_decode_track_ker
             const bool on = d < nd;
             const int dd = on ? d : 0, bin = track_pilot_bin(pi);
             const int l0 = 4 * (dd / 3), ln = l0 + 1 + dd % 3;
-            const float2 Y = reinterpret_cast<const float2 *>(re + ln * SDEC_SPEC_PITCH)[bin];
-            const float2 S = reinterpret_cast<const float2 *>(re + l0 * SDEC_SPEC_PITCH)[bin];
+            const float2 Y = reinterpret_cast<const float2 *>(re + ln * RXC_SPEC_PITCH)[bin];
+            const float2 S = reinterpret_cast<const float2 *>(re + l0 * RXC_SPEC_PITCH)[bin];
             float2 t = cmulc(Y, S);
             if ((TRACK_PILOT_NEG >> pi) & 1u) t = make_float2(-t.x, -t.y);
             t.x += __shfl_xor(t.x, 1, 64);
@@ -233,14 +142,8 @@ __global__ __launch_bounds__(64 * SDEC_BLOCK_WAVES) void stream_decode_track_ker
                 const int j = j0 + lane;
                 const bool ok = j < nsc;
                 const int jj = ok ? j : 0, d = jj / 48, m = jj - 48 * d, bin = data_bin(m);
-                const int l0 = 4 * (d / 3), ln = l0 + 1 + d % 3;
-                const float2 Y = reinterpret_cast<const float2 *>(re + ln * SDEC_SPEC_PITCH)[bin];
-                const float2 S = reinterpret_cast<const float2 *>(re + l0 * SDEC_SPEC_PITCH)[bin];
                 const float cx = __shfl(ux, 4 * d, 64), cy = __shfl(uy, 4 * d, 64);
-                const float r = __builtin_amdgcn_rcpf(fmaf(S.x, S.x, S.y * S.y));
-                const float g = ((SDEC_LTF_NEG >> bin) & 1ull) ? -2.0f * r : 2.0f * r;
-                const float2 u = cmulc(Y, S);
-                const float2 z0 = make_float2(u.x * g, u.y * g);
+                const float2 z0 = rxc_equalised(re, d, bin);
                 // u = 1 (the fallback) leaves Z as it is, a NaN or a signed zero included
                 const bool unit = cx == 1.f && cy == 0.f;
                 const float2 z = unit ? z0 : make_float2(fmaf(z0.x, cx, z0.y * cy), fmaf(z0.y, cx, -(z0.x * cy)));
@@ -265,49 +168,17 @@ __global__ __launch_bounds__(64 * SDEC_BLOCK_WAVES) void stream_decode_track_ker
             }
         }
         // ---- the packet's totals, its record and its counter terms ----
-        const float fe = sdec_sum_f(fev);
+        const float fe = rxc_sum_f(fev);
         uint32_t ferr = bev, fax = axv;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {
             ferr += (uint32_t)__shfl_xor((int)ferr, o, 64);
             fax += (uint32_t)__shfl_xor((int)fax, o, 64);
         }
-        if (lane == 0) {
-            const float N = 48.0f * (float)nd;
-            // a NaN sum (the stream ends before the long training symbols: S = 0, Z = 0 / 0) stays NaN, as the reference's
-            const float db = fe > 0.f ? fmaxf(3.01029995663981195214f * __builtin_amdgcn_logf(fe / N), -400.f)
-                                      : (fe == fe ? -400.f : fe);
-            const float dbp = fax > 0u ? 3.01029995663981195214f * __builtin_amdgcn_logf(2.0f * (float)fax / N) : -INFINITY;
-            ofdm_capture_result *r = &pkt->r;
-            r->bit_err = (int32_t)ferr;
-            r->post_axis_err = (int32_t)fax;
-            r->evm_pre_sum = fe;
-            r->evm_db_pre = db;
-            r->evm_db_post = dbp;
-            r->ber = (float)ferr / (96.0f * (float)nd);
-            if (a.counters) {
-                const float Q = (float)OFDM_EVM_Q_SCALE;             // x 2^20 is exact in fp32
-                atomicAdd(&acc[OFDM_C_FRAMES], 1ull);
-                atomicAdd(&acc[OFDM_C_SYMBOLS], (unsigned long long)nd);
-                atomicAdd(&acc[OFDM_C_BITS], 96ull * nd);
-                atomicAdd(&acc[OFDM_C_EVM_TERMS], 48ull * nd);
-                atomicAdd(&acc[OFDM_C_BIT_ERR], (unsigned long long)ferr);
-                atomicAdd(&acc[OFDM_C_FRAME_ERR], (unsigned long long)(ferr > 0u));
-                atomicAdd(&acc[OFDM_C_EVM_POST_AXIS], (unsigned long long)fax);
-                if (fabsf(fe) < INFINITY) {                          // a non-finite term is left out, never converted
-                    atomicAdd(&acc[OFDM_C_EVM_PRE_Q], (unsigned long long)__float2ll_rn(fe * Q));
-                    atomicAdd(&acc[OFDM_C_EVMDB_PRE_Q], (unsigned long long)__float2ll_rn(db * Q));
-                }
-                if (fax > 0u) {
-                    atomicAdd(&acc[OFDM_C_EVMDB_POST_Q], (unsigned long long)__float2ll_rn(dbp * Q));
-                    atomicAdd(&acc[OFDM_C_EVMDB_POST_FINITE], 1ull);
-                }
-            }
-        }
-        sdec_wave_sync();                                            // the next packet overwrites the planes
+        rxc_record(&pkt->r, acc, a.counters != nullptr, lane, nd, fe, ferr, fax);
+        rxc_wave_sync();                                             // the next packet overwrites the planes
     }
-    __syncthreads();
-    if (a.counters && threadIdx.x < SDEC_ACC_WORDS && acc[threadIdx.x]) atomicAdd(&a.counters[threadIdx.x], acc[threadIdx.x]);
+    rxc_flush(acc, a.counters);
 }
 
 static void track_launch(const StreamDecoder *dec, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const DecArgs &d,

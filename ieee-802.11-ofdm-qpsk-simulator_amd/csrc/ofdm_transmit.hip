@@ -193,27 +193,6 @@ __global__ __launch_bounds__(TXP_THREADS) void transmit_kernel(TxPkArgs a) {
     }
 }
 
-// rcosdesign(0.5, 10, 2, 'sqrt') (Tester.m:112; OFDM.c:32 holds the same values as floats), as ofdm_frame.hip
-static void txp_taps(float out[21]) {
-    const double beta = 0.5, sps = 2.0, pi = M_PI;
-    double h[21], e = 0.0;
-    for (int i = 0; i < 21; ++i) {
-        const double t = (i - 10) / sps, q = 4 * beta * t;
-        double b;
-        if (t == 0.0) b = -1.0 / (pi * sps) * (pi * (beta - 1) - 4 * beta);
-        else if (std::fabs(std::fabs(q) - 1.0) < 1e-12)
-            b = 1.0 / (2 * pi * sps) * (pi * (beta + 1) * std::sin(pi * (beta + 1) / (4 * beta)) -
-                                        4 * beta * std::sin(pi * (beta - 1) / (4 * beta)) +
-                                        pi * (beta - 1) * std::cos(pi * (beta - 1) / (4 * beta)));
-        else
-            b = -4 * beta / sps * (std::cos((1 + beta) * pi * t) + std::sin((1 - beta) * pi * t) / q) / (pi * (q * q - 1));
-        h[i] = b;
-        e += b * b;
-    }
-    for (int i = 0; i < 21; ++i) out[i] = (float)(h[i] / std::sqrt(e));
-    for (int i = 0; i < 10; ++i) out[20 - i] = out[i];
-}
-
 template <int CONV>
 static void launch_transmit(hipStream_t st, const TxPkArgs &a, bool impair, bool acc, unsigned grid) {
     const dim3 g(grid), b(TXP_THREADS);
@@ -270,7 +249,7 @@ extern "C" int ofdm_transmit_packets(ofdm_ctx *ctx, const ofdm_tx_opts *opts, co
     a.per_group = TXP_GROUP_SYMS / opts->n_data;
     a.groups = (n + a.per_group - 1) / a.per_group;
     a.stf_scale = (float)std::sqrt(13.0 / 6.0);
-    txp_taps(a.taps);
+    rrc_design(a.taps);
     // every block the same number of groups, and no more blocks than are resident at once
     const int64_t cap = (int64_t)TXP_BLOCKS_PER_CU * c->cus;
     const int64_t per_block = (a.groups + cap - 1) / cap;

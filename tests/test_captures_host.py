@@ -77,6 +77,9 @@ def test_capture_kernel_is_built_spill_free(pkg):
         assert not x["dump_variant"]                                   # no spill allowance
         assert not x.get("VGPRs Spill", 0) and not x.get("ScratchSize [bytes/lane]", 0), x["name"]
         assert x["VGPRs"] <= 256                                       # eight-wave blocks: two waves per SIMD
+    # the rows the shared chain (ofdm_rxchain.h) builds to
+    assert {x["name"]: (x["VGPRs"], x["LDS Size [bytes/block]"]) for x in rows} == {
+        "ofdm::capture_rx_kernel<true>": (235, 0), "ofdm::capture_rx_kernel<false>": (194, 0)}
 
 
 def test_reduce_capture_records_rule(pkg):

@@ -321,11 +321,12 @@ def test_timing_kernel_is_built_spill_free_and_the_stream_kernels_did_not_move(p
         assert not x["dump_variant"]
         assert not x.get("VGPRs Spill", 0) and not x.get("ScratchSize [bytes/lane]", 0), x["name"]
         assert x["VGPRs"] <= 128 and x["LDS Size [bytes/block]"] <= 16 * 1024          # four waves per SIMD at least
-    # the translation units whose host code takes the hook: their kernels' rows are what they were before it
+    # the translation units whose host code takes the hook: their kernels' rows are what they were before it (the decode
+    # kernels' rows are what the shared chain, ofdm_rxchain.h, builds to)
     want = {"ofdm::stream_detect_kernel<true>": (188, 64864), "ofdm::stream_detect_kernel<false>": (186, 64864),
             "ofdm::stream_select_kernel<0>": (42, 256), "ofdm::stream_select_kernel<1>": (74, 256),
-            "ofdm::stream_select_kernel<2>": (22, 256), "ofdm::stream_decode_kernel<true>": (233, 0),
-            "ofdm::stream_decode_kernel<false>": (192, 0), "ofdm::stream_detect_conj_kernel<true>": (193, 64992),
+            "ofdm::stream_select_kernel<2>": (22, 256), "ofdm::stream_decode_kernel<true>": (230, 0),
+            "ofdm::stream_decode_kernel<false>": (189, 0), "ofdm::stream_detect_conj_kernel<true>": (193, 64992),
             "ofdm::stream_detect_conj_kernel<false>": (186, 64992), "ofdm::stream_detect_thr_kernel<true>": (152, 64864),
             "ofdm::stream_detect_thr_kernel<false>": (152, 64864)}
     got = {x["name"]: (x["VGPRs"], x["LDS Size [bytes/block]"]) for x in report

@@ -14,8 +14,9 @@ outputs preallocated:
   none_plain    OFDM_TRACK_NONE without any optional output: stream_decode_kernel<false>
   pilots_bits   OFDM_TRACK_PILOTS with d_bits
   pilots_plain  OFDM_TRACK_PILOTS without any optional output (no d_phase either)
-  parent_bits, parent_plain   ofdm_receive_stream_timed of the library at --parent-lib (built from the parent commit),
-                loaded beside this one in the same process, a context of its own on the same stream
+  parent_bits, parent_plain, parent_pilots_bits, parent_pilots_plain   the same four calls into the library at
+                --parent-lib (built from the parent commit), loaded beside this one in the same process, a context of
+                its own on the same stream
 
 `--launches` launches per variant, interleaved, after a warm-up.  A launch is timed twice: the whole call between
 device events of the caller, and the decode kernel between the library's own events (ofdm_timing_query, reset before
@@ -42,12 +43,11 @@ UNITS_PER_CHUNK = 2048
 
 
 class ParentLib:
-    """The parent commit's library through ctypes alone (it has no ofdm_receive_stream_tracked to bind): the entry
-    points this tool needs, and a context of its own"""
+    """The parent commit's library through ctypes alone: the entry points this tool needs, and a context of its own"""
 
     def __init__(self, path, abi, stream_handle, message):
         self.lib = C.CDLL(str(path))
-        for name, (res, args) in {**abi._SIGS, **abi._LONG_SIGS, **abi._TIMING_SIGS}.items():
+        for name, (res, args) in {**abi._SIGS, **abi._LONG_SIGS, **abi._TRACK_SIGS}.items():
             fn = getattr(self.lib, name)
             fn.restype, fn.argtypes = res, args
         self.abi = abi
@@ -118,15 +118,10 @@ def main(argv=None) -> int:
         ptr = lambda t: C.c_void_p(t.data_ptr())
         ltf = abi.TIMING["ltf"]
 
-        def call(tracking, bits):
-            abi.check(eng.lib, eng.lib.ofdm_receive_stream_tracked(
-                eng.ctx, ptr(x), n, C.byref(opts), C.byref(conj), ltf, tracking, abi.PAYLOAD["message"], rows, ptr(pk), ptr(cnt),
+        def call(tracking, bits, who=eng):
+            abi.check(who.lib, who.lib.ofdm_receive_stream_tracked(
+                who.ctx, ptr(x), n, C.byref(opts), C.byref(conj), ltf, tracking, abi.PAYLOAD["message"], rows, ptr(pk), ptr(cnt),
                 ptr(words) if bits else None, None, None, None, None, None, None), "receive_stream_tracked")
-
-        def parent_call(bits):
-            abi.check(parent.lib, parent.lib.ofdm_receive_stream_timed(
-                parent.ctx, ptr(x), n, C.byref(opts), C.byref(conj), ltf, abi.PAYLOAD["message"], rows, ptr(pk), ptr(cnt),
-                ptr(words) if bits else None, None, None, None, None, None), "parent receive_stream_timed")
 
         none, pilots = abi.TRACKING["none"], abi.TRACKING["pilots"]
         # name -> (launch, who answers ofdm_timing_query, the decode kernel's id)
@@ -135,8 +130,10 @@ def main(argv=None) -> int:
                     "pilots_bits": (lambda: call(pilots, True), eng, abi.K_STREAM_DECODE_TRACK),
                     "pilots_plain": (lambda: call(pilots, False), eng, abi.K_STREAM_DECODE_TRACK)}
         if parent:
-            variants["parent_bits"] = (lambda: parent_call(True), parent, abi.K_STREAM_DECODE)
-            variants["parent_plain"] = (lambda: parent_call(False), parent, abi.K_STREAM_DECODE)
+            variants["parent_bits"] = (lambda: call(none, True, parent), parent, abi.K_STREAM_DECODE)
+            variants["parent_plain"] = (lambda: call(none, False, parent), parent, abi.K_STREAM_DECODE)
+            variants["parent_pilots_bits"] = (lambda: call(pilots, True, parent), parent, abi.K_STREAM_DECODE_TRACK)
+            variants["parent_pilots_plain"] = (lambda: call(pilots, False, parent), parent, abi.K_STREAM_DECODE_TRACK)
         found, errs = {}, {}
         for v, (f, _, _) in variants.items():                       # warm-up: code objects, scratch, the template
             f()
@@ -179,6 +176,10 @@ def main(argv=None) -> int:
               "decode_pilots_plain_over_baseline_bits": dm["pilots_plain"] / dm[f"{base}_bits"],
               "call_pilots_bits_over_baseline_bits": cm["pilots_bits"] / cm[f"{base}_bits"],
               "call_pilots_plain_over_baseline_plain": cm["pilots_plain"] / cm[f"{base}_plain"]}
+    if parent:                                                      # every decode variant of this library over the parent's own
+        for v, pv in (("none_bits", "parent_bits"), ("none_plain", "parent_plain"), ("pilots_bits", "parent_pilots_bits"),
+                      ("pilots_plain", "parent_pilots_plain")):
+            ratios[f"decode_{v}_over_{pv}"] = dm[v] / dm[pv]
     rec = {"samples": n, "stream_bytes": 8 * n, "data_symbols": nd, "gap": GAP, "snr_db": SNR_DB, "cfo_hz": CFO_HZ,
            "launches": a.launches, "detector": "conjugate", "timing": "ltf", "max_packets": rows,
            "packets_found_and_written": found, "bit_errors_of_the_records": errs,
