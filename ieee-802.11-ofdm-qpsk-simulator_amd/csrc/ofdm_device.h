@@ -137,6 +137,32 @@ __device__ __forceinline__ uint4 philox10_c2(const PhiloxMid &m, uint32_t wx, ui
     }
     return make_uint4(c0, c1, c2, c3);
 }
+// The same with round 3's c2 product staged.  Round 3's c2 = lo(M0 c0) ^ y is a function of the frame and of the
+// block index alone (c0 is the frame index's low word; no SNR index has reached it yet), so its product
+// p1 = M1 c2 is the same at every SNR point of the frame: philox_qword() computes it once per (frame, block index),
+//   q.x = hi(p1) ^ (k0 + 2 W0)        round 3: n0 = q.x ^ lo(M1 n2)
+//   q.y = lo(p1)                      round 3: c1 = q.y
+// and the overload below starts one step later, with the words x and z only (same output as philox10).
+__host__ __device__ inline uint2 philox_qword(uint32_t c0, uint32_t wy, uint32_t k0) {
+    const uint64_t p1 = (uint64_t)PHILOX_M1 * ((uint32_t)((uint64_t)PHILOX_M0 * c0) ^ wy);
+    return {(uint32_t)(p1 >> 32) ^ (k0 + 2u * PHILOX_W0), (uint32_t)p1};
+}
+__device__ __forceinline__ uint4 philox10_c2(const PhiloxMid &m, uint32_t wx, uint32_t wz, uint32_t qx, uint32_t qy,
+                                             uint32_t k0, uint32_t k1) {
+    const uint64_t p0r = (uint64_t)PHILOX_M0 * (m.p1hi ^ wx);
+    uint32_t c0 = qx ^ m.p1lo, c1 = qy, c2 = (uint32_t)(p0r >> 32) ^ wz, c3 = (uint32_t)p0r;
+    k0 += 3u * PHILOX_W0; k1 += 3u * PHILOX_W1;
+#pragma unroll
+    for (int r = 3; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0;
+        const uint64_t p1 = (uint64_t)PHILOX_M1 * c2;
+        const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
+        const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96);
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += PHILOX_W0; k1 += PHILOX_W1;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
 
 // Round keys k0 + r W0, k1 + r W1 (r = 0..9) held in VGPRs: a v_bitop3_b32 with an SGPR operand issues
 // at the slow rate, with three VGPR operands at the fast rate.  Built once per kernel

@@ -8,16 +8,65 @@ namespace ofdm {
 // Tx subcarrier value of fftshifted bin BIN for a symbol whose payload bits are w (MSB first):
 // QPSK data (OFDM.c:415-433), pilots {1,1,1,-1} (OFDM.c:523-544), nulls/DC 0; times (-1)^BIN for
 // the C ifft convention (D5).
+//
+// The QPSK map (D10) is 00:(+,+) 01:(-,+) 10:(-,-) 11:(+,-) times sgn / sqrt2: re > 0 iff b0 == b1, im > 0 iff
+// b0 == 0.  Both components are the constant 1/sqrt2 with one payload bit for a sign bit (im: b0, re: b0 ^ b1,
+// inverted where sgn = -1), so the map is a shift of the bit to position 31 and one v_bitop3_b32 per component,
+// a ^ (b & c) or a ^ (~b & c) with a = 1/sqrt2 and c = the sign mask: no compare, no select.
+struct TxSignSrc { uint32_t re, im; };
+// operand b of the two v_bitop3 for data subcarrier m: bit 31 is b0 ^ b1 (re) and b0 (im).  b0 and b1 are the
+// adjacent bits 31 - sh and 30 - sh of one payload word (2 m is even), so b0 ^ b1 is bit 31 - sh of w ^ (w << 1).
+__host__ __device__ constexpr TxSignSrc tx_sign_src(const uint32_t (&w)[3], int m) {
+    const uint32_t wd = w[(2 * m) >> 5];
+    const int sh = (2 * m) & 31;
+    return {(wd ^ (wd << 1)) << sh, wd << sh};
+}
+__host__ __device__ constexpr int tx_sign_tbl(int conv, int bin) { return (conv == OFDM_CONV_C && (bin & 1)) ? 0xD2 : 0x78; }
+// v_bitop3_b32 as the hardware defines it (bit (a, b, c) of the table), for the compile-time check below
+__host__ __device__ constexpr uint32_t bitop3_ref(uint32_t a, uint32_t b, uint32_t c, int tbl) {
+    uint32_t o = 0u;
+    for (int i = 0; i < 32; ++i) {
+        const uint32_t idx = (((a >> i) & 1u) << 2) | (((b >> i) & 1u) << 1) | ((c >> i) & 1u);
+        o |= (((uint32_t)tbl >> idx) & 1u) << i;
+    }
+    return o;
+}
+// the sign-bit form gives the bit patterns of the compare-and-select form of D10 for every data bin and bit pair,
+// whatever the other 94 payload bits are
+template <int CONV>
+__host__ __device__ constexpr bool tx_sign_map_is_d10() {
+    for (int bin = 0; bin < 64; ++bin) {
+        const int m = data_index(bin);
+        if (m < 0) continue;
+        const float sgn = (CONV == OFDM_CONV_C && (bin & 1)) ? -1.0f : 1.0f;
+        for (uint32_t bg = 0u; bg < 2u; ++bg)
+            for (uint32_t b0 = 0u; b0 < 2u; ++b0)
+                for (uint32_t b1 = 0u; b1 < 2u; ++b1) {
+                    uint32_t w[3] = {0u - bg, 0u - bg, 0u - bg};
+                    const int wi = (2 * m) >> 5, p0 = 31 - ((2 * m) & 31);
+                    w[wi] = (w[wi] & ~(3u << (p0 - 1))) | (b0 << p0) | (b1 << (p0 - 1));
+                    const float re = (b0 == b1) ? sgn * INV_SQRT2 : -sgn * INV_SQRT2;
+                    const float im = b0 ? -sgn * INV_SQRT2 : sgn * INV_SQRT2;
+                    const TxSignSrc s = tx_sign_src(w, m);
+                    const uint32_t c = __builtin_bit_cast(uint32_t, INV_SQRT2);
+                    if (bitop3_ref(c, s.re, 0x80000000u, tx_sign_tbl(CONV, bin)) != __builtin_bit_cast(uint32_t, re)) return false;
+                    if (bitop3_ref(c, s.im, 0x80000000u, tx_sign_tbl(CONV, bin)) != __builtin_bit_cast(uint32_t, im)) return false;
+                }
+    }
+    return true;
+}
+static_assert(tx_sign_map_is_d10<OFDM_CONV_C>() && tx_sign_map_is_d10<OFDM_CONV_MATLAB>(), "tx_bin's sign-bit map is D10's");
+
 template <int CONV, int BIN>
 __device__ __forceinline__ float2 tx_bin(const uint32_t (&w)[3]) {
     constexpr float sgn = (CONV == OFDM_CONV_C && (BIN & 1)) ? -1.0f : 1.0f;   // ifftshift+fftshift (D5)
     constexpr int m = data_index(BIN);
     if constexpr (m >= 0) {
-        const uint32_t b0 = bit_of(w, 2 * m), b1 = bit_of(w, 2 * m + 1);
-        // 00:(+,+) 01:(-,+) 10:(-,-) 11:(+,-): re > 0 iff b0 == b1, im > 0 iff b0 == 0 (D10)
-        const float re = (b0 == b1) ? sgn * INV_SQRT2 : -sgn * INV_SQRT2;
-        const float im = b0 ? -sgn * INV_SQRT2 : sgn * INV_SQRT2;
-        return make_float2(re, im);
+        const TxSignSrc s = tx_sign_src(w, m);
+        constexpr int TBL = tx_sign_tbl(CONV, BIN);
+        const uint32_t c = __float_as_uint(INV_SQRT2);
+        return make_float2(__uint_as_float(__builtin_amdgcn_bitop3_b32(c, s.re, 0x80000000u, TBL)),
+                           __uint_as_float(__builtin_amdgcn_bitop3_b32(c, s.im, 0x80000000u, TBL)));
     } else {
         return make_float2(sgn * pilot_at(BIN), 0.0f);    // pilots {1,1,1,-1}; nulls and DC 0
     }
@@ -52,8 +101,11 @@ __host__ __device__ constexpr int demap_bins() {
     for (int kc = 0; kc < 16; ++kc) n += data_index(4 * kc + R) >= 0;
     return n;
 }
+// demap_word_ref states what the word is, a bit at a time (the host reference); demap_word builds the same word by
+// moving whole two-bit fields: the pairs (b0, b0 ^ b1) of all 16 subcarriers of a payload word at once
+// (sign_fields), then one shift, mask and or per subcarrier.
 template <int R>
-__host__ __device__ inline uint32_t demap_word(const uint32_t w[3]) {
+__host__ __device__ inline uint32_t demap_word_ref(const uint32_t w[3]) {
     uint32_t t = 0u;
     int pos = 31;
     for (int kc = 0; kc < 16; ++kc) {
@@ -63,6 +115,25 @@ __host__ __device__ inline uint32_t demap_word(const uint32_t w[3]) {
         const uint32_t b1 = (w[(2 * m + 1) >> 5] >> (31 - ((2 * m + 1) & 31))) & 1u;
         t |= b0 << pos;
         t |= (b0 ^ b1) << (pos - 1);
+        pos -= 2;
+    }
+    return t;
+}
+// subcarrier m's field of a payload word is bits 31 - 2 (m & 15) and the one below: (b0, b1) -> (b0, b0 ^ b1)
+__host__ __device__ constexpr uint32_t sign_fields(uint32_t w) { return (w & 0xAAAAAAAAu) | ((w ^ (w >> 1)) & 0x55555555u); }
+// the field whose low bit is `from`, moved to low bit `to`
+__host__ __device__ constexpr uint32_t field_to(uint32_t f, int from, int to) {
+    return (to >= from ? f << (to - from) : f >> (from - to)) & (3u << to);
+}
+template <int R>
+__host__ __device__ inline uint32_t demap_word(const uint32_t w[3]) {
+    const uint32_t f[3] = {sign_fields(w[0]), sign_fields(w[1]), sign_fields(w[2])};
+    uint32_t t = 0u;
+    int pos = 30;
+    for (int kc = 0; kc < 16; ++kc) {
+        const int m = data_index(4 * kc + R);
+        if (m < 0) continue;
+        t |= field_to(f[m >> 4], 30 - 2 * (m & 15), pos);
         pos -= 2;
     }
     return t;
@@ -83,7 +154,8 @@ __host__ __device__ constexpr int pair_bin(int p) {
 // Pair-order truth words of one symbol (Tx rows 7..9): for each pair p, bins k then 64 - k, each as
 // (b0, b0 ^ b1) MSB first -- 4 bits per pair, 8 pairs per word (the demap_word signs, D10).  Read by the packed
 // Rayleigh receiver; the packed AWGN receivers take the same signs from the clean spectra (demap_bin).
-__host__ __device__ inline void pair_words(const uint32_t w[3], uint32_t t[3]) {
+// (pair_words_ref: a bit at a time, the host reference; pair_words: the same words by two-bit field moves)
+__host__ __device__ inline void pair_words_ref(const uint32_t w[3], uint32_t t[3]) {
     t[0] = t[1] = t[2] = 0u;
     for (int p = 0; p < PACK_PAIRS; ++p)
         for (int h = 0; h < 2; ++h) {
@@ -93,6 +165,15 @@ __host__ __device__ inline void pair_words(const uint32_t w[3], uint32_t t[3]) {
             const uint32_t b1 = (w[(2 * m + 1) >> 5] >> (31 - ((2 * m + 1) & 31))) & 1u;
             const int pos = 31 - 4 * (p & 7) - 2 * h;
             t[p >> 3] |= (b0 << pos) | ((b0 ^ b1) << (pos - 1));
+        }
+}
+__host__ __device__ inline void pair_words(const uint32_t w[3], uint32_t t[3]) {
+    const uint32_t f[3] = {sign_fields(w[0]), sign_fields(w[1]), sign_fields(w[2])};
+    t[0] = t[1] = t[2] = 0u;
+    for (int p = 0; p < PACK_PAIRS; ++p)
+        for (int h = 0; h < 2; ++h) {
+            const int m = data_index(h ? 64 - pair_bin(p) : pair_bin(p));
+            t[p >> 3] |= field_to(f[m >> 4], 30 - 2 * (m & 15), 30 - 4 * (p & 7) - 2 * h);
         }
 }
 

@@ -167,6 +167,13 @@ __device__ __forceinline__ Noise4 pack_noise(const PhiloxMid &md, cwords *w, uin
     const u4v v = *w;
     return noise4_of(philox10_c2(md, v.x, v.y, v.z, k0, k1), K);
 }
+// The LS AWGN receiver: round 3's c2 product is the same at every SNR point of a frame (ofdm_device.h
+// philox_qword), staged per (block index, frame) by the item's prologue: one per-lane 8-byte read q beside the
+// broadcast read of the words (x, z).
+__device__ __forceinline__ Noise4 pack_noise(const PhiloxMid &md, lcu2 *w, lcu2 *q, uint32_t k0, uint32_t k1, float K) {
+    const u2v v = *w, u = *q;
+    return noise4_of(philox10_c2(md, v.x, v.y, u.x, u.y, k0, k1), K);
+}
 
 #ifdef OFDM_PACK_STAMPS   // diagnostic build: s_memtime per item phase, per wave role, summed over the grid
 #include <cstdio>
@@ -201,6 +208,9 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
     static_assert(!FADE || KIND == 2, "the packed Rayleigh receiver is the LS one");
     // where the next item's L2 warm-up is issued (see the SNR loop)
     constexpr bool WLATE = KIND == 2 && !FADE;
+    // the LS AWGN receiver stages round 3's c2 products of the item's 64 frames (pack_noise); the other two have no
+    // LDS to spare (Rayleigh: two blocks per CU at 81,168 B; ideal CSI: three at 53 KB) and keep the words (x, y, z)
+    constexpr bool QW = KIND == 2 && !FADE;
     __shared__ __attribute__((aligned(16))) float4 spec[PACK_PAIRS][2][PK_FRAMES];   // 48 KB: (C[k], C[64-k])
     __shared__ __attribute__((aligned(16))) float4 ce[PACK_PAIRS];                   // LS: FFT((-1)^n 2T[n])
     __shared__ __attribute__((aligned(16))) float4 fce[FADE ? PACK_PAIRS : 1][FADE ? PK_FRAMES : 1];  // 24 KB: H' FFT(2T)
@@ -217,7 +227,8 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
         const int c = ln % SUBN;
         return SUBN > 1 && c > 0 && q < SACC_XQ ? &sacx[q][5 * (c - 1)] : sacc[q];
     };
-    __shared__ __attribute__((aligned(16))) u4v wlds[PACK_BLOCKS];   // the item's Philox words
+    __shared__ __attribute__((aligned(16))) std::conditional_t<QW, u2v, u4v> wlds[PACK_BLOCKS];   // the item's Philox words
+    __shared__ __attribute__((aligned(8))) u2v qw[QW ? PACK_BLOCKS : 1][QW ? PK_FRAMES : 1];     // 24 KB: philox_qword
     __shared__ uint32_t pf_dummy[64];                             // L2 warm-up destination (never read)
     // 8 B of LDS that a pruned option's array held in every measured build (round 6, profiles/r06/README.md): kept,
     // with its per-iteration address, so that the code objects stay byte-identical to the PMC-certified builds
@@ -283,6 +294,20 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
         // loop (they would be the only values spilled)
         int t = tid;
         opaque(t);
+        if constexpr (QW) {
+            // round 3's c2 products of the item's frames (lane t & 63 holds frame t & 63 in the SNR loop), 12 of the
+            // 48 table slots per wave; y from the item's row of the launch's table
+            if (uniform_hi) {
+                const uint32_t flo = (uint32_t)fg + (uint32_t)(t & 63);
+                const int s0 = (PACK_BLOCKS / 4) * wv;
+#pragma unroll
+                for (int i = 0; i < PACK_BLOCKS / 4; ++i) {
+                    const uint2 qv = philox_qword(flo, a.philox_words[row * PACK_BLOCKS + s0 + i].y, a.k0);
+                    u2v o; o.x = qv.x; o.y = qv.y;
+                    qw[s0 + i][t & 63] = o;
+                }
+            }
+        }
         // kernel arguments read where used through an opaque kernarg pointer: hoisted, the 40 words of each
         // TxArgs would be held in SGPRs across the item loop and spill
         using KArgs = const __attribute__((address_space(4))) RxArgs;
@@ -340,8 +365,11 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
                     else tx_symbol<OFDM_CONV_MATLAB>(ap->nx, sidx);
                 }
             }
-            if (uniform_hi && j >= 64 && j < 64 + PACK_BLOCKS)       // wave 3: the item's row
-                wlds[j - 64] = ((const u4v *)a.philox_words)[row * PACK_BLOCKS + (j - 64)];
+            if (uniform_hi && j >= 64 && j < 64 + PACK_BLOCKS) {     // wave 3: the item's row
+                const u4v v = ((const u4v *)a.philox_words)[row * PACK_BLOCKS + (j - 64)];
+                if constexpr (QW) { u2v o; o.x = v.x; o.y = v.z; wlds[j - 64] = o; }
+                else wlds[j - 64] = v;
+            }
             if constexpr (FADE) {      // the group's channel responses, a frame's 24 pairs split over waves 2 / 3
                 const int fr = j & 63;
                 const uint64_t ff = a.first_frame + (uint64_t)(grp * PK_FRAMES + fr);
@@ -376,7 +404,8 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
         const uint64_t f = a.first_frame + (uint64_t)fl;
         auto snr_loop = [&](auto fastc) __attribute__((always_inline)) {
         constexpr bool FAST = decltype(fastc)::value;
-        cwords *wtab = (cwords *)&wlds[0];
+        using WordsP = std::conditional_t<QW, lcu2, cwords> *;
+        WordsP wtab = (WordsP)&wlds[0];
         for (int q = wv + 4 * sub; q < a.n_snr; q += 4 * ns) {
             // LS AWGN: wave 2 warms L2 with the next item's rows at the start of its last SNR iteration, one
             // iteration before the next prologue reads them (warmed in the prologue, a whole item earlier, most
@@ -388,7 +417,8 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
                     KArgsW *apw = (KArgsW *)__builtin_amdgcn_kernarg_segment_ptr();
                     if (nx < n_items && apw->own.n_sym == 0) {
                         const int64_t ng = nx < R * B ? nx : R * B + (nx - R * B) / S;
-                        const int ln = lane;
+                        int ln = lane;
+                        opaque(ln);     // the eight per-lane row addresses are formed here, not held across the items
 #pragma unroll
                         for (int i = 0; i < 8; ++i) {
                             const int line = ln + 64 * i;                      // 0..511
@@ -407,9 +437,12 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
             const PhiloxMid md = philox_mid(hd);
             // block index `blk` of table slot `slot` (a literal); the words' LDS address goes through an opaque copy
             // where a stage starts, so that the stage's reads stay inside it (as sp's do)
-            cwords *wt = wtab;
+            WordsP wt = wtab;
+            lcu2 *qp = (lcu2 *)&qw[0][QW ? lane : 0];
             auto noise = [&](uint32_t blk, int slot, float Kn) __attribute__((always_inline)) {
-                if constexpr (FAST) return pack_noise(md, wt + slot, a.k0, a.k1, Kn);
+                // (both branches are compiled in every instantiation: the casts name the type each is taken with)
+                if constexpr (FAST && QW) return pack_noise(md, (lcu2 *)(wt + slot), qp + slot * PK_FRAMES, a.k0, a.k1, Kn);
+                else if constexpr (FAST) return pack_noise(md, (cwords *)(wt + slot), a.k0, a.k1, Kn);
                 else return pack_noise(hd, blk, a.k0, a.k1, Kn);
             };
             // ---- LTF pair noise (LS): e[n] = sqrt2 sigma x Gaussian 192 + n (block 48 + n/4), packed as
@@ -425,6 +458,7 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
                     uint32_t tg = 48u + 2 * i;
                     if constexpr (FAST) opaque(wt);
                     else opaque(tg);
+                    if constexpr (FAST && QW) opaque(qp);
                     // blocks b = 2i, 2i+1 (z[4i..4i+3]) and b + 8 (z[4i+16..4i+19])
                     static_for<0, 2>([&](auto hc) {
                         constexpr int h = decltype(hc)::value;
@@ -468,6 +502,7 @@ __global__ __launch_bounds__(256, KIND == 2 ? (CHAN == OFDM_CHAN_RAYLEIGH4 ? OFD
                 uint32_t tg = 84u + g;
                 if constexpr (FAST) opaque(wt);
                 else opaque(tg);
+                if constexpr (FAST && QW) opaque(qp);
                 static_for<0, 4>([&](auto Qc) {
                     constexpr int Q = decltype(Qc)::value;
                     const Noise4 n0 = noise(tg + 4 * Q, 16 + g + 4 * Q, K);
