@@ -24,8 +24,9 @@ constexpr int LONG_MAX_FRAMES = OFDM_LONG_MAX_DATA_SYMBOLS;
 constexpr int LONG_MSG_MAX_CHARS = OFDM_LONG_MSG_MAX_CHARS;
 static_assert(LONG_MSG_MAX_CHARS == 12 * LONG_MAX_FRAMES, "12 characters per data symbol");
 int payload_table_long(int payload, const std::string &message, uint32_t table[3 * LONG_MAX_FRAMES]);
-// rcosdesign(0.5, 10, 2, 'sqrt') (Tester.m:112; OFDM.c:32 holds the same values as floats): the 21 RRC taps of the
-// capture and stream receivers and of the packet and fading transmitters
+// rcosdesign(0.5, 10, 2, 'sqrt') (Tester.m:112; OFDM.c:32 holds the same values as floats): the 21 RRC taps of frame
+// mode, of the capture and stream receivers and of the packet and fading transmitters; symmetric to the bit (the sync
+// kernels fold them)
 void rrc_design(float out[21]);
 // The errors of a data symbol that reaches the demapper as 64 exact zeros (its window lies wholly past the end of the
 // samples; ofdm_rxchain.h rxc_totals): the reference's slicer decides "-" on both axes for a zero (Z > 0 fails,

@@ -1,14 +1,19 @@
 // ofdm_fading.hip -- K10, K11: the per-packet fading transmitter and its tap generator
 // (include/ofdm_mi355x_fading.h).
 //
-//   K10 transmit_faded_kernel : ofdm_transmit.hip's transmit_kernel (K7) with a FIR of its own for every packet between
-//                        the RRC filter and the packet's gain and carrier offset.
+//   K10 transmit_faded_kernel : the packet transmitter with a FIR of its own for every packet between the RRC filter
+//                        and the packet's gain and carrier offset.
 //   K11 draw_taps_kernel : Rayleigh taps from the Philox stream of symbol mode's channel_taps (ofdm_rxcommon.h), one
 //                        lane per (packet, pair of taps): one Philox block is four Gaussians, two complex taps.
 //
-// K10 keeps K7's block shape, group loop, IFFT and polyphase RRC pass with K7's arithmetic (restated here, as
-// ofdm_stream.hip restates ofdm_captures.hip: K7's translation unit does not move).  Per packet:
-//   filter   K7's pass; the lane's pair (e0, e1) = w[2 q], w[2 q + 1] goes to an LDS packet buffer instead of HBM.
+// K10 keeps K7's block shape, group loop, IFFT and polyphase RRC pass with K7's arithmetic (ofdm_transmit.hip describes
+// them); constants, sign table, txc_zero_pads, txc_at, txc_aligned16, txc_phasor and the host routines are
+// ofdm_txchain.h's, as K7's are.  The group, packet and filter text stands in this body as in K7's: called from the
+// header the instances read the whole argument block at the entry, took 1 to 6 more VGPRs, and every accumulate variant
+// measured slower, the 32-tap ones 0.7 to 0.8 %, outside the former spread ("The shared transmit chain").  As
+// written the eight instances are the machine code they were before the header existed, byte for byte;
+// tests/test_gpu_fading.py holds K10's samples to K7's bit for bit.  Per packet:
+//   filter   K7's pass; the lane's pair (e0, e1) = w[2 q], w[2 q + 1] goes to an LDS packet buffer, not to HBM.
 //            The buffer holds [H + 4 zeros | w[0 .. P) | H + 4 zeros], H = n_taps - 1; the zeros are written once per
 //            block (D and n_taps are the launch's) and the pass only ever writes the P samples in the middle.
 //   fir      ofdm_channel.hip's shape (K8): a lane owns the four consecutive outputs 4 Q .. 4 Q + 3, keeps a window of
@@ -17,46 +22,33 @@
 //            the window moves by register renaming and the step's four LDS reads are issued ahead of its 64 fmaf.
 //            The packet's taps are read from HBM once per packet, lane l of every wave holding tap l; the loop
 //            broadcasts tap j with two v_readlane.
-//   rotate   K7's phasor on sample m = 4 Q + s, counted from the packet's first sample.
+//   rotate   K7's phasor (txc_phasor) on sample m = 4 Q + s, counted from the packet's first sample.
 //   store    two 16-byte stores per lane when the quad's address is 16-byte aligned -- a property of the packet --
 //            and guarded 8-byte stores when not, at the recording's ends and in the packet's last quad.
 //   add      OFDM_TX_ACCUMULATE: the wave's 256 samples are 512 floats; they are re-dealt with lane shuffles so
-//            that each of eight atomic wave-instructions adds 64 consecutive floats, K7's shape.
+//            that each of eight atomic wave-instructions adds 64 consecutive floats (K7 deals 4 x 2 floats per lane the
+//            same way; the two shuffle patterns share no text).
 // Two barriers per packet: the FIR pass reads what every lane of the filter pass wrote, and the next packet's
 // filter pass overwrites it.
-#include "ofdm_internal.h"
-#include "ofdm_ctx.h"
-#include "ofdm_rxcommon.h"
-#include "ofdm_phasor.h"
+#include "ofdm_txchain.h"
 #include "ofdm_mi355x_fading.h"
 #include <algorithm>
-#include <cmath>
 
 namespace ofdm {
 
-constexpr int FD_THREADS = 256;
-constexpr int FD_GROUP_SYMS = 62;           // data symbols per group: lanes 0..61 of wave 0; 62, 63: STF, LTF
-constexpr int FD_ROW = 65;                  // LDS pitch of a time symbol (complex samples)
-constexpr int FD_PAD = 10;                  // (RRC taps - 1) / 2: zeros in front of and behind the frame
-constexpr int FD_PRE = 0;                   // [10 zeros | 320 preamble samples]
-constexpr int FD_ZERO = FD_PRE + FD_PAD + 320;
-constexpr int FD_ROWS = FD_ZERO + FD_PAD;
-constexpr int FD_SYMS = FD_ROWS + 64 * FD_ROW;                                // K7's 4,500 complex samples
-constexpr int FD_MAX_P = 2 * (320 + 80 * LONG_MAX_FRAMES) + 20;               // 3,060
+// the launch's own constants (tests/test_scale_host.py reads them in this file)
+constexpr int FD_GROUP_SYMS = 62;           // data symbols per group: the chain's lanes 0..61 of wave 0
+constexpr int FD_BLOCKS_PER_CU = 2;         // resident blocks the launch is sized for (LDS: 2 x 61,040 B of 160 KiB)
+static_assert(FD_GROUP_SYMS == TXC_GROUP_SYMS, "lanes 62 and 63 of wave 0 are the training symbols' rows");
+constexpr int FD_MAX_P = txc_packet_len(LONG_MAX_FRAMES);                     // 3,060
 // [H + 4 zeros | P | H + 4 zeros]: the history of n_taps - 1 samples on either side, in front the up to three samples
 // more that a step of four taps reads, behind the up to three that the last quad's window reaches
 constexpr int FD_BUF = FD_MAX_P + 2 * (OFDM_FADE_MAX_TAPS - 1) + 8;           // 3,130
-constexpr int FD_LDS = FD_SYMS + FD_BUF;                                      // 7,630 complex samples = 61,040 B
-constexpr int FD_BLOCKS_PER_CU = 2;         // resident blocks the launch is sized for (LDS: 2 x 61,040 B of 160 KiB)
+constexpr int FD_LDS = TXC_LDS + FD_BUF;                                      // 7,630 complex samples = 61,040 B
 static_assert(8 * FD_LDS <= 65536, "static LDS of one block");
 
-// short training tones S_k at bins 6..58 (OFDM.c:483-490), as ofdm_transmit.hip
-__host__ __device__ constexpr int fd_stf_sign(int bin) {
-    constexpr int8_t S[53] = {0, 0, 1, 0, 0, 0, -1, 0, 0, 0, 1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 0, 0, 1, 0, 0, 0, 0,
-                              0, 0, 0, -1, 0, 0, 0, -1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0};
-    return (bin >= 6 && bin <= 58) ? S[bin - 6] : 0;
-}
-
+// TxPkArgs' members with h and n_taps among them, in this kernel's own order: as TxPkArgs with the two behind it, only
+// the prologue changed and every store variant measured 0.8 to 1.9 % slower ("The shared transmit chain")
 struct FadeArgs {
     const uint32_t *words;       // [n][3 D]
     const int64_t *pos;          // [n] or null
@@ -71,34 +63,25 @@ struct FadeArgs {
     float taps[21];              // the RRC filter
 };
 
-// g exp(j 2 pi f m Ts), as ofdm_transmit.hip
-__device__ __forceinline__ float2 fd_phasor(bool has_gain, float2 g, bool has_cfo, double f, int m) {
-    const float2 e = has_cfo ? carrier_phasor(f, (double)m) : make_float2(1.0f, 0.0f);
-    return has_gain ? cmul(g, e) : e;
-}
-
 __device__ __forceinline__ float fd_lane(float v, int l) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
 template <int CONV, bool IMPAIR, bool ACC>
-__global__ __launch_bounds__(FD_THREADS) void transmit_faded_kernel(FadeArgs a) {
+__global__ __launch_bounds__(TXC_THREADS) void transmit_faded_kernel(FadeArgs a) {
     __shared__ float2 lds[FD_LDS];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int D = a.n_data, nfr = 320 + 80 * D, half = nfr + FD_PAD, P = 2 * half;
+    const int D = a.n_data, nfr = 320 + 80 * D, half = nfr + TXC_PAD, P = 2 * half;
     const int L = a.n_taps, H = L - 1, PL = P + H, quads = (PL + 3) >> 2, off = H + 4;     // w[0] at buf[off]
-    float2 *const T = lds + FD_ROWS;
-    float2 *const buf = lds + FD_SYMS;
-    if (tid < FD_PAD) {
-        lds[FD_PRE + tid] = make_float2(0.f, 0.f);
-        lds[FD_ZERO + tid] = make_float2(0.f, 0.f);
-    }
-    for (int i = tid; i < FD_BUF; i += FD_THREADS) buf[i] = make_float2(0.f, 0.f);
+    float2 *const T = lds + TXC_ROWS;
+    float2 *const buf = lds + TXC_LDS;
+    txc_zero_pads(lds);
+    for (int i = tid; i < FD_BUF; i += TXC_THREADS) buf[i] = make_float2(0.f, 0.f);
     bool first = true;
     for (int64_t grp = blockIdx.x; grp < a.groups; grp += gridDim.x) {
         const int64_t g0 = grp * a.per_group;
         const int np = (int)min((int64_t)a.per_group, a.n - g0);
-        // ---------------------------------------------------------------- the group's time symbols (K7)
+        // ---------------------------------------------------------------- the group's time symbols (K7's text)
         if (tid < 64) {
             const bool is_data = tid < np * D, is_pre = first && tid >= FD_GROUP_SYMS;
             if (is_data || is_pre) {
@@ -112,7 +95,7 @@ __global__ __launch_bounds__(FD_THREADS) void transmit_faded_kernel(FadeArgs a) 
                     constexpr int i = decltype(ic)::value;
                     constexpr float sgn = (CONV == OFDM_CONV_C && (i & 1)) ? -1.0f : 1.0f;   // D5
                     const float2 data = tx_bin<CONV, i>(w);
-                    const float s = sgn * a.stf_scale * (float)fd_stf_sign(i);
+                    const float s = sgn * a.stf_scale * (float)txc_stf_sign(i);
                     X[i] = is_data ? data
                          : tid == FD_GROUP_SYMS ? make_float2(s, s)                           // (1+j) S_k scale
                          : make_float2(sgn * (float)ltf_sign(i), 0.f);                        // L_k
@@ -120,16 +103,16 @@ __global__ __launch_bounds__(FD_THREADS) void transmit_faded_kernel(FadeArgs a) 
                 fft64<true>(X);
                 static_for<0, 64>([&](auto nc) {
                     constexpr int n = decltype(nc)::value;
-                    T[tid * FD_ROW + n] = cscale(X[digit_rev4(n)], (n & 1) ? -1.0f / 64.0f : 1.0f / 64.0f);
+                    T[tid * TXC_ROW + n] = cscale(X[digit_rev4(n)], (n & 1) ? -1.0f / 64.0f : 1.0f / 64.0f);
                 });
             }
         }
         __syncthreads();
         if (first) {
             // short = first 16 samples x10, long = [T(32:64) T T] (Preamble_Generator, OFDM.c:392-398)
-            for (int n = tid; n < 320; n += FD_THREADS)
-                lds[FD_PRE + FD_PAD + n] = n < 160 ? T[FD_GROUP_SYMS * FD_ROW + (n & 15)]
-                                                   : T[(FD_GROUP_SYMS + 1) * FD_ROW + ((n - 160 + 32) & 63)];
+            for (int n = tid; n < 320; n += TXC_THREADS)
+                lds[TXC_PRE + TXC_PAD + n] = n < 160 ? T[FD_GROUP_SYMS * TXC_ROW + (n & 15)]
+                                                     : T[(FD_GROUP_SYMS + 1) * TXC_ROW + ((n - 160 + 32) & 63)];
             __syncthreads();
             first = false;
         }
@@ -143,18 +126,10 @@ __global__ __launch_bounds__(FD_THREADS) void transmit_faded_kernel(FadeArgs a) 
             const double fk = has_cfo ? (double)a.cfo[pk] : 0.0;
             // lane l of every wave: tap l of this packet
             const float2 hv = lane < L ? a.h[pk * L + lane] : make_float2(0.f, 0.f);
-            const int rows = FD_ROWS + g * D * FD_ROW;
-            // frame index n -> LDS index; n in [-10, nfr + 10)
-            auto at = [&](int n, int &run) -> int {      // run: how far below n the map stays contiguous
-                if (n < 320) { run = FD_PAD; return FD_PRE + FD_PAD + n; }
-                if (n >= nfr) { run = n - nfr; return FD_ZERO + run; }
-                const int x = n - 320, d = (int)(__umul24((unsigned)x, 52429u) >> 22), j = x - 80 * d;   // x / 80, x < 2^13
-                run = j >= 16 ? j - 16 : j;
-                return rows + d * FD_ROW + (j >= 16 ? j - 16 : j + 48);                                   // [x(48:64) x]
-            };
-            for (int q = tid; q < half; q += FD_THREADS) {
+            const int rows = TXC_ROWS + g * D * TXC_ROW;
+            for (int q = tid; q < half; q += TXC_THREADS) {
                 int run, unused;
-                const int a0 = at(q, run), a10 = at(q - FD_PAD, unused) + FD_PAD;
+                const int a0 = txc_at(q, nfr, rows, run), a10 = txc_at(q - TXC_PAD, nfr, rows, unused) + TXC_PAD;
                 float2 x[11];
 #pragma unroll
                 for (int t = 0; t < 11; ++t) x[t] = lds[(t <= run ? a0 : a10) - t];
@@ -174,8 +149,8 @@ __global__ __launch_bounds__(FD_THREADS) void transmit_faded_kernel(FadeArgs a) 
                 buf[off + 2 * q + 1] = e1;
             }
             __syncthreads();
-            const bool vec = (((uintptr_t)a.out + 8u * (uint64_t)pos) & 15u) == 0;
-            for (int qb = 0; qb < quads; qb += FD_THREADS) {
+            const bool vec = txc_aligned16(a.out, pos);
+            for (int qb = 0; qb < quads; qb += TXC_THREADS) {
                 const int Q = qb + tid;
                 if (Q - lane >= quads) continue;         // whole waves: the tap broadcast and the shuffles read every lane
                 const int Qc = min(Q, quads - 1);
@@ -212,7 +187,7 @@ __global__ __launch_bounds__(FD_THREADS) void transmit_faded_kernel(FadeArgs a) 
                 }
                 if (IMPAIR) {
 #pragma unroll
-                    for (int s = 0; s < 4; ++s) y[s] = cmul(fd_phasor(has_gain, gk, has_cfo, fk, 4 * Qc + s), y[s]);
+                    for (int s = 0; s < 4; ++s) y[s] = cmul(txc_phasor(has_gain, gk, has_cfo, fk, 4 * Qc + s), y[s]);
                 }
                 if (!ACC) {
                     const int m0 = 4 * Q;
@@ -280,29 +255,16 @@ __global__ __launch_bounds__(256) void draw_taps_kernel(DrawArgs a) {
     }
 }
 
-template <int CONV>
-static void launch_faded(hipStream_t st, const FadeArgs &a, bool impair, bool acc, unsigned grid) {
-    const dim3 g(grid), b(FD_THREADS);
-    if (impair) {
-        if (acc) hipLaunchKernelGGL((transmit_faded_kernel<CONV, true, true>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((transmit_faded_kernel<CONV, true, false>), g, b, 0, st, a);
-    } else {
-        if (acc) hipLaunchKernelGGL((transmit_faded_kernel<CONV, false, true>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((transmit_faded_kernel<CONV, false, false>), g, b, 0, st, a);
-    }
-}
-
 }  // namespace ofdm
 
 using namespace ofdm;
 
 extern "C" int ofdm_faded_len(int32_t n_data, int32_t n_taps, int32_t *len) {
     if (!len) return set_error(OFDM_E_ARG, "len is NULL");
-    if (n_data < 1 || n_data > LONG_MAX_FRAMES)
-        return set_error(OFDM_E_ARG, "n_data %d outside [1, %d]", n_data, LONG_MAX_FRAMES);
+    if (const int rc = txc_check_n_data(n_data)) return rc;
     if (n_taps < 1 || n_taps > OFDM_FADE_MAX_TAPS)
         return set_error(OFDM_E_ARG, "n_taps %d outside [1, %d]", n_taps, OFDM_FADE_MAX_TAPS);
-    *len = 2 * (320 + 80 * n_data) + 20 + n_taps - 1;
+    *len = txc_packet_len(n_data) + n_taps - 1;
     return OFDM_OK;
 }
 
@@ -345,49 +307,20 @@ extern "C" int ofdm_transmit_faded(ofdm_ctx *ctx, const ofdm_tx_opts *opts, cons
                                    const void *d_cfo_hz, const void *d_taps, int32_t n_taps, void *d_out,
                                    int64_t n_out) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c) return set_error(OFDM_E_ARG, "ctx is NULL");
-    if (!opts) return set_error(OFDM_E_ARG, "opts is NULL");
-    if (n < 0) return set_error(OFDM_E_ARG, "n %lld is negative", (long long)n);
-    if (n_out < 0) return set_error(OFDM_E_ARG, "n_out %lld is negative", (long long)n_out);
-    if (opts->n_data < 1 || opts->n_data > LONG_MAX_FRAMES)
-        return set_error(OFDM_E_ARG, "n_data %d outside [1, %d]", opts->n_data, LONG_MAX_FRAMES);
-    if (opts->conv != OFDM_CONV_C && opts->conv != OFDM_CONV_MATLAB) return set_error(OFDM_E_ARG, "bad conv %d", opts->conv);
-    if (opts->flags & ~OFDM_TX_ACCUMULATE) return set_error(OFDM_E_ARG, "unknown flag bits 0x%x", opts->flags & ~OFDM_TX_ACCUMULATE);
-    if (n_taps < 1 || n_taps > OFDM_FADE_MAX_TAPS)
-        return set_error(OFDM_E_ARG, "n_taps %d outside [1, %d]", n_taps, OFDM_FADE_MAX_TAPS);
-    if (!d_words && n > 0) return set_error(OFDM_E_ARG, "d_words is required");
-    if (!d_taps && n > 0) return set_error(OFDM_E_ARG, "d_taps is required");
-    if (reinterpret_cast<uintptr_t>(d_taps) & 7u) return set_error(OFDM_E_ARG, "d_taps must be 8-byte aligned");
-    if (!d_out && n_out > 0) return set_error(OFDM_E_ARG, "d_out is required");
-    if (reinterpret_cast<uintptr_t>(d_out) & 7u) return set_error(OFDM_E_ARG, "d_out must be 8-byte aligned");
+    const TxcTapArgs fir{d_taps, n_taps, OFDM_FADE_MAX_TAPS};
+    if (const int rc = txc_check_args(c, opts, d_words, n, d_out, n_out, &fir)) return rc;
     if (n == 0 || n_out == 0) return OFDM_OK;
     if (hipSetDevice(c->device) != hipSuccess) return set_error(OFDM_E_HIP, "hipSetDevice(%d) failed", c->device);
 
     FadeArgs a{};
-    a.words = (const uint32_t *)d_words;
-    a.pos = (const int64_t *)d_pos;
-    a.gain = (const float2 *)d_gain;
-    a.cfo = (const float *)d_cfo_hz;
+    txc_fill(a, opts, FD_GROUP_SYMS / opts->n_data, d_words, n, d_pos, pos0, stride, d_gain, d_cfo_hz, d_out, n_out);
     a.h = (const float2 *)d_taps;
-    a.out = (float2 *)d_out;
-    a.n = n;
-    a.n_out = n_out;
-    a.pos0 = pos0;
-    a.stride = stride;
-    a.n_data = opts->n_data;
-    a.per_group = FD_GROUP_SYMS / opts->n_data;
-    a.groups = (n + a.per_group - 1) / a.per_group;
     a.n_taps = n_taps;
-    a.stf_scale = (float)std::sqrt(13.0 / 6.0);
-    rrc_design(a.taps);
-    // every block the same number of groups, and no more blocks than are resident at once
-    const int64_t cap = (int64_t)FD_BLOCKS_PER_CU * c->cus;
-    const int64_t per_block = (a.groups + cap - 1) / cap;
-    const unsigned grid = (unsigned)((a.groups + per_block - 1) / per_block);
-    const bool impair = d_gain || d_cfo_hz, acc = (opts->flags & OFDM_TX_ACCUMULATE) != 0;
+    const dim3 grid(txc_grid(a.groups, (int64_t)FD_BLOCKS_PER_CU * c->cus)), block(TXC_THREADS);
     c->tic(OFDM_K_FADE);
-    if (opts->conv == OFDM_CONV_C) launch_faded<OFDM_CONV_C>(c->stream, a, impair, acc, grid);
-    else launch_faded<OFDM_CONV_MATLAB>(c->stream, a, impair, acc, grid);
+    txc_dispatch(opts, d_gain || d_cfo_hz, [&](auto conv, auto impair, auto acc) {
+        hipLaunchKernelGGL((transmit_faded_kernel<conv(), impair(), acc()>), grid, block, 0, c->stream, a);
+    });
     c->toc();
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(OFDM_E_HIP, "transmit_faded_kernel launch: %s", hipGetErrorString(e));

@@ -28,6 +28,9 @@
 #if defined(OFDM_FRAME_SYM_TU) || defined(OFDM_FRAME_FIX_TU) || defined(OFDM_FRAME_LONG_TU) || defined(OFDM_FRAME_XL_TU)
 #define OFDM_FRAME_AUX_TU 1
 #endif
+#ifndef OFDM_FRAME_AUX_TU
+#include "ofdm_txchain.h"   // K4a's time symbols
+#endif
 
 namespace ofdm {
 
@@ -45,13 +48,6 @@ constexpr int CAP_ABS_MAX = 6000;            // LDS budget of the capture (>= ca
 constexpr int FR_XL_MAX_DATA = LONG_MAX_FRAMES;
 constexpr int FR_XL_MAX = 320 + 80 * FR_XL_MAX_DATA;
 constexpr int CAP_XL_MAX = 9400;             // >= cap_len_for(FR_XL_MAX_DATA) = 9394
-
-// short training tones S_k at bins 6..58 (OFDM.c:483-490): +-1 on every 4th tone, times (1+j)
-__host__ __device__ constexpr int stf_sign(int bin) {
-    constexpr int8_t S[53] = {0, 0, 1, 0, 0, 0, -1, 0, 0, 0, 1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 0, 0, 1, 0, 0, 0, 0,
-                              0, 0, 0, -1, 0, 0, 0, -1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0};
-    return (bin >= 6 && bin <= 58) ? S[bin - 6] : 0;
-}
 
 struct WaveArgs {
     float2 *wave;        // [wave_len_for(n_data)]
@@ -156,22 +152,7 @@ __global__ __launch_bounds__(256) void frame_wave_kernel(WaveArgs a) {
     if (tid < 2 + a.n_data) {
         const int ds = tid < 2 ? 0 : tid - 2;
         const uint32_t w[3] = {a.table[3 * ds], a.table[3 * ds + 1], a.table[3 * ds + 2]};
-        float2 X[64];
-        static_for<0, 64>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            constexpr float sgn = (CONV == OFDM_CONV_C && (i & 1)) ? -1.0f : 1.0f;   // D5
-            const float2 data = tx_bin<CONV, i>(w);
-            const float s = sgn * a.stf_scale * (float)stf_sign(i);
-            const float2 v = tid == 0 ? make_float2(s, s)                                   // (1+j) S_k scale
-                           : tid == 1 ? make_float2(sgn * (float)ltf_sign(i), 0.f)          // L_k
-                           : data;
-            X[i] = v;
-        });
-        fft64<true>(X);
-        static_for<0, 64>([&](auto nc) {
-            constexpr int n = decltype(nc)::value;
-            T[tid][n] = cscale(X[digit_rev4(n)], (n & 1) ? -1.0f / 64.0f : 1.0f / 64.0f);
-        });
+        txc_time_symbol<CONV>(tid >= 2, tid == 0, w, a.stf_scale, T[tid]);
     }
     __syncthreads();
     // frame = [S(160) L(160) D_0(80) .. D_{nd-1}(80)] (OFDM.c:569-583); short = first 16 samples x10,
@@ -1062,7 +1043,7 @@ __global__ __launch_bounds__(64 * W, FRAME_SYNC_MINW) void frame_sync_kernel(Fra
         // reads past its buffer iff the last instant does, and the last sample is always needed. ----
         const bool dbg = !FIX && a.dbg_frame && first_item;
         bool oob_l = false;
-        // the RRC taps are symmetric (h[t] = h[20 - t], OFDM.c:32; rrc_taps), so a window is 10 pair sums + the
+        // the RRC taps are symmetric (h[t] = h[20 - t], OFDM.c:32; rrc_design), so a window is 10 pair sums + the
         // centre tap: 11 FMAs per component instead of 21
         float tv[11];
         {
@@ -1850,31 +1831,9 @@ constexpr int FRAME_LONG_REGION = 3072;                // LW_RING + LW_EXT
 constexpr int LONG_TABLE_REACH = 2048;
 constexpr int FRAME_LONG_MIN_CAP = 4100;     // captures longer than this (frames of >= 5 data symbols) run it
 
-// ======================================================================== host side
-// rcosdesign(0.5, 10, 2, 'sqrt') (Tester.m:112; OFDM.c:32 holds the same values as floats)
-static void rrc_taps(float out[21]) {
-    const double beta = 0.5, sps = 2.0, pi = M_PI;
-    double h[21], e = 0.0;
-    for (int i = 0; i < 21; ++i) {
-        const double t = (i - 10) / sps;
-        double b;
-        if (t == 0.0) b = -1.0 / (pi * sps) * (pi * (beta - 1) - 4 * beta);
-        else if (std::fabs(std::fabs(4 * beta * t) - 1.0) < 1e-12)
-            b = 1.0 / (2 * pi * sps) * (pi * (beta + 1) * std::sin(pi * (beta + 1) / (4 * beta)) -
-                                        4 * beta * std::sin(pi * (beta - 1) / (4 * beta)) +
-                                        pi * (beta - 1) * std::cos(pi * (beta - 1) / (4 * beta)));
-        else
-            b = -4 * beta / sps * (std::cos((1 + beta) * pi * t) + std::sin((1 - beta) * pi * t) / (4 * beta * t)) /
-                (pi * ((4 * beta * t) * (4 * beta * t) - 1));
-        h[i] = b;
-        e += b * b;
-    }
-    for (int i = 0; i < 21; ++i) out[i] = (float)(h[i] / std::sqrt(e));
-    for (int i = 0; i < 10; ++i) out[20 - i] = out[i];      // symmetric (the sync kernel folds the taps)
-}
-
 }  // namespace ofdm
 
+// ======================================================================== host side
 using namespace ofdm;
 
 #define HIPOK(expr)                                                                             \
@@ -1899,7 +1858,7 @@ static int ensure_wave(Ctx *c, int conv, int payload) {
     if (rc) return rc;
     a.wave = (float2 *)c->d_wave;
     a.power = (double *)((char *)c->d_wave + (size_t)len * sizeof(float2));
-    rrc_taps(a.taps);
+    rrc_design(a.taps);
     a.stf_scale = (float)std::sqrt(13.0 / 6.0);
     if (conv == OFDM_CONV_C) hipLaunchKernelGGL(frame_wave_kernel<OFDM_CONV_C>, dim3(1), dim3(256), 0, c->stream, a);
     else hipLaunchKernelGGL(frame_wave_kernel<OFDM_CONV_MATLAB>, dim3(1), dim3(256), 0, c->stream, a);
@@ -1950,7 +1909,7 @@ static void fill_frame_args(XlArgs &xa, Ctx *c, const ofdm_rx_opts *o, int noise
     a.word_stats = o->word_stats ? 1 : 0;
     // the lazy capture's equivalence test runs the same sweep with it switched off (tests/test_gpu_frame.py)
     a.no_lazy = getenv("OFDM_FRAME_NO_LAZY") != nullptr;
-    rrc_taps(a.taps);
+    rrc_design(a.taps);
 }
 
 // bits needed for the largest magnitude, as OFDM.c:56-64
@@ -2299,7 +2258,7 @@ int ofdm_word_length_report(ofdm_ctx *ctx, const float *capture, int32_t cap_len
     float *dout = (float *)((char *)c->d_scratch2 + bytes);
     HIPOK(hipMemcpyAsync(dx, capture, bytes, hipMemcpyHostToDevice, c->stream));
     FrameArgs a{};
-    rrc_taps(a.taps);
+    rrc_design(a.taps);
     hipLaunchKernelGGL(word_length_kernel, dim3(1), dim3(256), 0, c->stream, (const float2 *)dx, (int)cap_len, a, dout);
     HIPOK(hipGetLastError());
     float mm[2];
