@@ -38,6 +38,7 @@ K_FADE, K_DRAW_TAPS = 10, 11                                     # OFDM_K_FADE, 
 K_STREAM_DETECT_CONJ = 12                                        # OFDM_K_STREAM_DETECT_CONJ (ofdm_mi355x_detect.h)
 K_STREAM_TIMING = 13                                             # OFDM_K_STREAM_TIMING (ofdm_mi355x_timing.h)
 K_STREAM_DECODE_TRACK = 14                                       # OFDM_K_STREAM_DECODE_TRACK (ofdm_mi355x_track.h)
+K_STREAM_DETECT_DIV, K_STREAM_TIMING_DIV, K_STREAM_DECODE_DIV = 15, 16, 17   # OFDM_K_STREAM_*_DIV (ofdm_mi355x_diversity.h)
 
 # every entry point of the header, with ctypes argument types
 _V = C.c_void_p
@@ -174,6 +175,16 @@ _TRACK_SIGS = {
 }
 TRACK_EXPORTS = tuple(_TRACK_SIGS)
 TRACKING = {"none": 0, "pilots": 1}              # OFDM_TRACK_NONE, OFDM_TRACK_PILOTS
+
+# the extension header include/ofdm_mi355x_diversity.h (receive diversity: 2 to 4 recordings combined in the stream
+# receiver); the export lists above and ABI_VERSION do not change with it
+DIVERSITY_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_diversity.h"
+_DIVERSITY_SIGS = {
+    "ofdm_receive_stream_diversity": (C.c_int, [_V, C.POINTER(_V), C.c_int32, C.c_int64, _V, _V, C.c_int, C.c_int, C.c_int,
+                                                C.c_int64, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+}
+DIVERSITY_FUNCTIONS = tuple(_DIVERSITY_SIGS)
+DIVERSITY_MAX_BRANCHES = 4                       # OFDM_DIVERSITY_MAX_BRANCHES
 
 
 class OfdmError(RuntimeError):
@@ -392,7 +403,8 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
                         "there is no CPU fallback")
     lib = C.CDLL(str(p))
     for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS,
-                              **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS, **_TIMING_SIGS, **_TRACK_SIGS}.items():
+                              **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS, **_TIMING_SIGS, **_TRACK_SIGS,
+                              **_DIVERSITY_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

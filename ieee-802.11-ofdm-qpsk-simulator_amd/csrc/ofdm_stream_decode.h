@@ -1,8 +1,9 @@
-// ofdm_stream_decode.h -- what only the stream receiver's two decode kernels share: stream_decode_kernel
-// (ofdm_stream.hip) and stream_decode_track_kernel (ofdm_stream_track.hip, the pilot-tracking decode of
-// include/ofdm_mi355x_track.h).  The argument block stream_receive prepares, and the part of a packet's chain that
-// comes before ofdm_rxchain.h's stages: reading the packet's record, staging its samples, the matched filter on the
-// staged planes and the sync half of the record.
+// ofdm_stream_decode.h -- what only the stream receiver's decode kernels share: stream_decode_kernel (ofdm_stream.hip),
+// stream_decode_track_kernel (ofdm_stream_track.hip, the pilot-tracking decode of include/ofdm_mi355x_track.h) and
+// stream_decode_div_kernel (ofdm_stream_div.hip, the diversity decode of include/ofdm_mi355x_diversity.h).  The argument
+// block stream_receive prepares, and the part of a packet's chain that comes before ofdm_rxchain.h's stages: reading
+// the packet's record, staging its samples, the matched filter on the staged planes and the sync half of the record;
+// and the pilots' bins and signs for the pilot step of the two tracking decodes.
 #pragma once
 #include <cmath>
 #include "ofdm_mi355x_stream.h"
@@ -85,6 +86,17 @@ __device__ __forceinline__ void sdec_filter(const float *re, const float *im, co
         fim[ii] = vy;
     }
 }
+
+// the pilots' bins (pilot_at, ofdm_device.h) and p_k L_k, for the pilot step of the tracking decodes
+// (ofdm_stream_track.hip, ofdm_stream_div.hip)
+__device__ __forceinline__ int track_pilot_bin(int i) { return 11 + 14 * i; }
+static_assert(pilot_at(11) == 1.f && pilot_at(25) == 1.f && pilot_at(39) == 1.f && pilot_at(53) == -1.f, "pilots {1,1,1,-1} at 11, 25, 39, 53");
+constexpr uint32_t track_pilot_neg() {
+    uint32_t v = 0;
+    for (int i = 0; i < 4; ++i) v |= (uint32_t)(pilot_at(11 + 14 * i) * (float)ltf_sign(11 + 14 * i) < 0.f) << i;
+    return v;
+}
+constexpr uint32_t TRACK_PILOT_NEG = track_pilot_neg();
 
 // the sync half of the record and its counter term leave ahead of the transforms, so nothing of it stays live over them
 __device__ __forceinline__ void sdec_sync_record(ofdm_capture_result *r, unsigned long long *acc, bool counters, int lane,

@@ -1,5 +1,6 @@
 // ofdm_stream_detect.h -- what ofdm_stream.hip (ofdm_receive_stream), ofdm_stream_conj.hip (ofdm_receive_stream_ex),
-// ofdm_stream_timing.hip (ofdm_receive_stream_timed) and ofdm_stream_track.hip (ofdm_receive_stream_tracked) share: the
+// ofdm_stream_timing.hip (ofdm_receive_stream_timed), ofdm_stream_track.hip (ofdm_receive_stream_tracked) and
+// ofdm_stream_div.hip (ofdm_receive_stream_diversity, which fills all three hooks) share: the
 // detection kernels' argument block, the hook through which the extended entry point replaces the detection launch
 // alone, the hook through which the timed one adds a launch between the selection and the decode, and the hook through
 // which the tracked one replaces the decode launch.  The selection and decode kernels stay in ofdm_stream.hip and are
@@ -30,6 +31,7 @@ struct StreamDetector {
     float threshold;
     void (*launch)(const StreamDetector *det, dim3 grid, hipStream_t stream, const DetArgs &a);
     const char *name;              // for the launch error's text
+    const void *user;              // the hook's own (ofdm_stream_div.hip: the branch table), nullptr for the existing ones
 };
 
 // What a refiner's launch works on: the recording, and the records stream_select_kernel<2> has just written.
@@ -50,6 +52,7 @@ struct StreamRefiner {
     void (*launch)(const StreamRefiner *ref, Ctx *c, hipStream_t stream, const RefineArgs &a);
     const char *name;              // for the launch error's text
     void *out;                     // the refiner's own output (optional)
+    const void *user;              // as StreamDetector's
 };
 
 // Another decode kernel in place of stream_decode_kernel (ofdm_stream_track.hip: the pilot-tracking decode of
@@ -63,6 +66,7 @@ struct StreamDecoder {
                    const uint32_t *payload);
     const char *name;              // for the launch error's text
     void *out;                     // the decoder's own output (optional)
+    const void *user;              // as StreamDetector's
 };
 
 // ofdm_receive_stream's body; det == nullptr is the reference's rule with stream_detect_kernel, ref == nullptr no

@@ -18,40 +18,13 @@
 #include "ofdm_mi355x_timing.h"
 #include "ofdm_ctx.h"
 #include "ofdm_stream_detect.h"
+#include "ofdm_stream_ltf.h"
 
 namespace ofdm {
 
 constexpr int TM_WAVES = 4;                                   // packets per block and sweep
 constexpr int TM_BLOCKS_PER_CU = 8;                           // the grid's cap: the waves loop past it
-constexpr int TM_CAND = OFDM_TIMING_BACK + OFDM_TIMING_FWD;   // 64: one candidate per lane
-constexpr int TM_LTF = 394;                                   // 2 * 192 + 10: the first long training symbol in the waveform
-constexpr int TM_FIRST = TM_LTF - 16 - OFDM_TIMING_BACK;      // 322: candidate 0 reads from p + 322
-constexpr int TM_LEN = 256, TM_SEG = 32, TM_NSEG = TM_LEN / TM_SEG, TM_PERIOD = 128;
-constexpr int TM_WINDOW = TM_CAND - 1 + TM_LEN;               // 319 samples staged per packet
-constexpr int TM_PLANE = 320;
-constexpr int TM_LOADS = (TM_WINDOW + 63) / 64;
-static_assert(TM_CAND == 64, "lane = candidate");
-static_assert(TM_FIRST == 322 && TM_FIRST + TM_WINDOW - 1 == 640, "the search window is [p + 322, p + 640]");
-static_assert(TM_WINDOW <= TM_PLANE && (TM_CAND - 1) + (TM_LEN - 1) < TM_WINDOW, "every lane's last sample is staged");
-static_assert(sizeof(ofdm_stream_timing) == 16, "ofdm_stream_timing is 16 bytes");
 static_assert(OFDM_K_STREAM_TIMING == Ctx::K_STREAM_TIMING && Ctx::K_STREAM_TIMING < Ctx::NK, "the timing kernel's id is one of the context's");
-
-struct TimArgs {
-    const float2 *x;
-    int64_t n;
-    const int64_t *count;          // d_count: [1] records to refine
-    ofdm_stream_packet *pk;
-    ofdm_stream_timing *out;       // optional
-    float te[TM_NSEG];             // sum_k |t[32 s + k]|^2
-    float2 t[TM_PERIOD];           // the template's period: t[k] = P[k mod 128]
-};
-
-// LDS ordering between the lanes of one wave (the block's other waves run other packets)
-__device__ __forceinline__ void tm_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ __launch_bounds__(64 * TM_WAVES) void stream_timing_kernel(TimArgs a) {
     __shared__ float planes[TM_WAVES][2][TM_PLANE];
@@ -138,21 +111,37 @@ __global__ __launch_bounds__(64 * TM_WAVES) void stream_timing_kernel(TimArgs a)
     }
 }
 
-// w[394 .. 522) of the context's own Transmitter() waveform (frame_wave_kernel through ofdm_transmitter) under the
-// convention CONV, once per context and convention: the two templates are cached side by side
-template <int CONV>
-static int timing_prepare(const StreamRefiner *, Ctx *c) {
-    static_assert(CONV == OFDM_CONV_C || CONV == OFDM_CONV_MATLAB, "one cached template per convention");
-    if (c->ltf_ready[CONV]) return OFDM_OK;
+// ofdm_stream_ltf.h: the template from the context's own Transmitter() waveform (frame_wave_kernel through
+// ofdm_transmitter)
+int timing_template(Ctx *c, int conv) {
+    if (c->ltf_ready[conv]) return OFDM_OK;
     std::vector<float2> w(10 * (2 * (320 + 80 * LONG_MAX_FRAMES) + 20));
     int32_t len = 0;
-    int rc = ofdm_transmitter(reinterpret_cast<ofdm_ctx *>(c), CONV, OFDM_PAYLOAD_MESSAGE, 1,
+    int rc = ofdm_transmitter(reinterpret_cast<ofdm_ctx *>(c), conv, OFDM_PAYLOAD_MESSAGE, 1,
                               reinterpret_cast<float *>(w.data()), (int32_t)w.size(), &len);
     if (rc) return rc;
     if (len < TM_LTF + TM_PERIOD) return set_error(OFDM_E_HIP, "Transmitter() gave %d samples, the template needs %d", len, TM_LTF + TM_PERIOD);
-    std::copy(w.begin() + TM_LTF, w.begin() + TM_LTF + TM_PERIOD, c->ltf_template[CONV]);
-    c->ltf_ready[CONV] = true;
+    std::copy(w.begin() + TM_LTF, w.begin() + TM_LTF + TM_PERIOD, c->ltf_template[conv]);
+    c->ltf_ready[conv] = true;
     return OFDM_OK;
+}
+
+void timing_fill(const Ctx *c, int conv, TimArgs &a) {
+    std::copy(c->ltf_template[conv], c->ltf_template[conv] + TM_PERIOD, a.t);
+    for (int s = 0; s < TM_NSEG; ++s) {
+        double e = 0.0;
+        for (int k = 0; k < TM_SEG; ++k) {
+            const float2 v = a.t[(TM_SEG * s + k) & (TM_PERIOD - 1)];
+            e += (double)v.x * v.x + (double)v.y * v.y;
+        }
+        a.te[s] = (float)e;
+    }
+}
+
+template <int CONV>
+static int timing_prepare(const StreamRefiner *, Ctx *c) {
+    static_assert(CONV == OFDM_CONV_C || CONV == OFDM_CONV_MATLAB, "one cached template per convention");
+    return timing_template(c, CONV);
 }
 
 template <int CONV>
@@ -163,15 +152,7 @@ static void timing_launch(const StreamRefiner *ref, Ctx *c, hipStream_t stream, 
     a.count = r.count;
     a.pk = r.pk;
     a.out = (ofdm_stream_timing *)ref->out;
-    std::copy(c->ltf_template[CONV], c->ltf_template[CONV] + TM_PERIOD, a.t);
-    for (int s = 0; s < TM_NSEG; ++s) {
-        double e = 0.0;
-        for (int k = 0; k < TM_SEG; ++k) {
-            const float2 v = a.t[(TM_SEG * s + k) & (TM_PERIOD - 1)];
-            e += (double)v.x * v.x + (double)v.y * v.y;
-        }
-        a.te[s] = (float)e;
-    }
+    timing_fill(c, CONV, a);
     // the packet count stays on the device: enough blocks for max_packets, at most TM_BLOCKS_PER_CU per CU; the waves loop
     const int64_t blocks = (r.max_packets + TM_WAVES - 1) / TM_WAVES;
     const dim3 grid((unsigned)std::min<int64_t>(blocks, TM_BLOCKS_PER_CU * (int64_t)c->cus));

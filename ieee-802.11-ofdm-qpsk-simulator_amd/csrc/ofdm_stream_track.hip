@@ -50,16 +50,6 @@ struct TrackArgs {
     uint32_t words[3 * RXC_MAX_DATA];   // the payload, MSB first, three words per data symbol
 };
 
-// the pilots' bins (pilot_at, ofdm_device.h) and p_k L_k
-__device__ __forceinline__ int track_pilot_bin(int i) { return 11 + 14 * i; }
-static_assert(pilot_at(11) == 1.f && pilot_at(25) == 1.f && pilot_at(39) == 1.f && pilot_at(53) == -1.f, "pilots {1,1,1,-1} at 11, 25, 39, 53");
-constexpr uint32_t track_pilot_neg() {
-    uint32_t v = 0;
-    for (int i = 0; i < 4; ++i) v |= (uint32_t)(pilot_at(11 + 14 * i) * (float)ltf_sign(11 + 14 * i) < 0.f) << i;
-    return v;
-}
-constexpr uint32_t TRACK_PILOT_NEG = track_pilot_neg();
-
 __global__ __launch_bounds__(64 * RXC_MAX_WAVES) void stream_decode_track_kernel(TrackArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long strk_smem[];
     unsigned long long *acc = strk_smem;

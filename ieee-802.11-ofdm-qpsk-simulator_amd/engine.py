@@ -636,6 +636,166 @@ class Engine:
                 _ptr(pk), _ptr(cnt), opt(words), opt(eq), opt(counters), opt(metric), opt(cross)), "receive_stream_ex")
         return pk, cnt, words, eq, metric, cross, tim, ph
 
+    def _branch_tensors(self, branches) -> list:
+        """The B recordings of receive_diversity as one-dimensional complex64 device tensors of one length: a [B, n]
+        complex64 tensor with unit stride along n and 8-byte-aligned rows, a sequence of B one-dimensional tensors, or
+        a numpy [B, n] array (uploaded once).  ValueError for anything else, before any launch."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        if isinstance(branches, np.ndarray):
+            if branches.dtype != np.complex64 or branches.ndim != 2:
+                raise ValueError(f"branches must be complex64 [B, n], got {branches.dtype} {branches.shape}")
+            branches = torch.from_numpy(np.ascontiguousarray(branches)).to(dev)
+        if torch.is_tensor(branches):
+            if branches.dim() != 2:
+                raise ValueError(f"branches must be complex64 [B, n], got {tuple(branches.shape)}")
+            rows = list(branches.unbind(0))
+        elif isinstance(branches, (list, tuple)) and all(torch.is_tensor(r) for r in branches):
+            rows = list(branches)
+            if any(r.dim() != 1 for r in rows):
+                raise ValueError("a sequence of one-dimensional tensors expected")
+        else:
+            raise ValueError(f"branches must be a [B, n] tensor, a sequence of tensors or a numpy array, got "
+                             f"{type(branches).__name__}")
+        if not 1 <= len(rows) <= abi.DIVERSITY_MAX_BRANCHES:
+            raise ValueError(f"1 to {abi.DIVERSITY_MAX_BRANCHES} branches expected, got {len(rows)}")
+        n = int(rows[0].shape[0])
+        for b, r in enumerate(rows):
+            if r.dtype != torch.complex64:
+                raise ValueError(f"branch {b} must be complex64, got {r.dtype}")
+            if r.device != dev:
+                raise ValueError(f"branch {b} is on {r.device}, the engine runs on {dev}")
+            if int(r.shape[0]) != n:
+                raise ValueError(f"branches of one length expected, branch {b} has {int(r.shape[0])} samples, branch 0 {n}")
+            if n > 1 and r.stride(0) != 1:
+                raise ValueError(f"branch {b} needs a unit stride along its samples, got {r.stride(0)}")
+            if n and r.data_ptr() % 8:
+                raise ValueError(f"branch {b} must be 8-byte aligned")
+        return rows
+
+    def receive_diversity(self, branches, mode: str = "c", payload: str = "message", max_packets: int | None = None,
+                          want_bits: bool = True, want_eq: bool = False, want_metric: bool = False,
+                          want_cross: bool = False, counters=None, keep_device: bool = False,
+                          opts: dict | None = None, detector: str = "reference", threshold: float = 0.75,
+                          timing: str = "none", tracking: str = "none") -> dict:
+        """receive_stream over B = 1..4 recordings of the same packets, one per antenna, on a common sample clock and
+        oscillator (ofdm_receive_stream_diversity, include/ofdm_mi355x_diversity.h): the conjugate detector's sums, the
+        fine timing metric and the carrier offset correlations are summed over the branches, and the branches'
+        spectra are combined with maximal-ratio weights before the slicer (stream.diversity_metric,
+        stream.refine_timing_branches and stream.combine_branches are the rules).  With one branch the call is
+        receive_stream's on that recording.
+        branches: a [B, n] complex64 tensor on this engine's device with unit stride along n and 8-byte-aligned rows, a
+        sequence of B one-dimensional such tensors of equal length, or a numpy complex64 [B, n] array, uploaded once.
+        Anything else raises ValueError before any launch, as does B > 1 with a detector other than "conjugate" (the
+        reference's metric carries the channel's phase: its branch sums would cancel).  The other arguments and the result are receive_stream's, plus gain (float32 [count, B]: every
+        branch's mean |H|^2 over the 52 used subcarriers; None for B = 1) and, with keep_device, d_gain."""
+        torch = _torch()
+        opts = make_rx_opts(mode, opts=opts)
+        nd = self.payload_frames(payload)
+        dev = torch.device("cuda", self.device)
+        from_numpy = isinstance(branches, np.ndarray)
+        rows = self._branch_tensors(branches)
+        n = int(rows[0].shape[0])
+        max_packets = self._div_max_packets(n, max_packets)
+        if counters is not None:
+            if not (torch.is_tensor(counters) and counters.dtype == torch.int64 and counters.device == dev
+                    and counters.numel() == abi.NCOUNTERS and counters.is_contiguous()):
+                raise ValueError("counters must be a contiguous int64 device tensor of NCOUNTERS elements")
+        sopts = abi.make_stream_opts(detector, threshold)
+        tcode, kcode = abi.timing_code(timing), abi.tracking_code(tracking)
+        if len(rows) > 1 and detector != "conjugate":
+            raise ValueError(f"{len(rows)} branches need detector='conjugate', got {detector!r}")
+        lc = abi.stream_positions(n, detector)
+        pk, cnt, words, eq, metric, cross, tim, ph, gain = self._launch_receive_diversity(
+            rows, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross, counters, sopts, tcode, kcode)
+        found, count = (int(v) for v in cnt.cpu())
+        records = pk[:count].cpu().numpy().view(abi.stream_packet_dtype()).reshape(count)
+        bits = messages = None
+        if want_bits:
+            sh = torch.arange(31, -1, -1, dtype=torch.int32, device=dev)
+            bits = ((words[:count].unsqueeze(-1) >> sh) & 1).reshape(count, 96 * nd)          # MSB first
+            host = bits.cpu().numpy()
+            messages = [decode_message(row) for row in host]
+            if from_numpy:
+                bits = host
+        eq = None if eq is None else eq[:count]
+        metric = None if metric is None else metric[:lc]
+        cross = None if cross is None else cross[:(lc + 31) // 32]
+        if from_numpy:
+            eq = None if eq is None else eq.cpu().numpy()
+            metric = None if metric is None else metric.cpu().numpy()
+            cross = None if cross is None else cross.cpu().numpy().view(np.uint32)
+        out = dict(count=count, found=found, positions=records["packet_pos"].copy(), records=records, bits=bits,
+                   eq=eq, messages=messages, metric=metric, cross=cross, frames=nd, coarse_pos=None, shift=None,
+                   quality=None, phase=None, gain=None, branches=len(rows))
+        if ph is not None:
+            out.update(phase=ph[:count].cpu().numpy())
+        if gain is not None:
+            out.update(gain=gain[:count].cpu().numpy())
+        if tim is not None:
+            trows = tim[:count].cpu().numpy().view(abi.stream_timing_dtype()).reshape(count)
+            out.update(coarse_pos=trows["coarse_pos"].copy(), shift=trows["shift"].copy(), quality=trows["quality"].copy())
+        if keep_device:
+            out.update(d_packets=pk, d_count=cnt, d_words=words, d_timing=tim, d_phase=ph, d_gain=gain)
+        return out
+
+    def receive_diversity_device(self, branches, mode: str = "c", payload: str = "message",
+                                 max_packets: int | None = None, counters=None, detector: str = "reference",
+                                 threshold: float = 0.75, timing: str = "none", tracking: str = "none") -> dict:
+        """receive_diversity for device recordings without the read-back: nothing waits for the device.  Returns what
+        receive_stream_device returns -- d_packets, d_count, d_words, frames, d_timing, d_phase -- and d_gain (float32
+        [rows, B], None for B = 1)."""
+        opts = make_rx_opts(mode)
+        nd = self.payload_frames(payload)
+        if isinstance(branches, np.ndarray):
+            raise ValueError("branches must be device tensors")
+        rows = self._branch_tensors(branches)
+        max_packets = self._div_max_packets(int(rows[0].shape[0]), max_packets)
+        sopts = abi.make_stream_opts(detector, threshold)
+        tcode, kcode = abi.timing_code(timing), abi.tracking_code(tracking)
+        if len(rows) > 1 and detector != "conjugate":
+            raise ValueError(f"{len(rows)} branches need detector='conjugate', got {detector!r}")
+        out = self._launch_receive_diversity(rows, opts, payload, nd, max_packets, True, False, False, False, counters,
+                                             sopts, tcode, kcode)
+        return dict(d_packets=out[0], d_count=out[1], d_words=out[2], frames=nd, d_timing=out[6], d_phase=out[7],
+                    d_gain=out[8])
+
+    @staticmethod
+    def _div_max_packets(n: int, max_packets) -> int:
+        if max_packets is None:
+            max_packets = n // 301 + 1
+        if int(max_packets) != max_packets or max_packets < 0:
+            raise ValueError(f"max_packets must be a non-negative integer, got {max_packets!r}")
+        return int(max_packets)
+
+    def _launch_receive_diversity(self, rows, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross,
+                                  counters, sopts, timing, tracking):
+        """Allocates ofdm_receive_stream_diversity's outputs and enqueues it: _launch_receive_stream's tuple and the
+        gains (float32 [rows, B], None for one branch)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        nb, n = len(rows), int(rows[0].shape[0])
+        conj = sopts.detector == abi.DETECTOR["conjugate"]
+        lc = abi.stream_positions(n, "conjugate" if conj else "reference")
+        nrows = max(max_packets, 1)                                   # a pointer even when nothing may be written
+        pk = torch.empty((nrows, C.sizeof(abi.StreamPacket)), dtype=torch.uint8, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        words = torch.empty((nrows, 3 * nd), dtype=torch.int32, device=dev) if want_bits else None
+        eq = torch.empty((nrows, 48 * nd), dtype=torch.complex64, device=dev) if want_eq else None
+        metric = torch.empty(max(lc, 1), dtype=torch.float32, device=dev) if want_metric else None
+        cross = torch.empty(max((lc + 31) // 32, 1), dtype=torch.int32, device=dev) if want_cross else None
+        tim = torch.empty((nrows, C.sizeof(abi.StreamTiming)), dtype=torch.uint8, device=dev) \
+            if timing != abi.TIMING["none"] else None
+        ph = torch.empty((nrows, nd), dtype=torch.float32, device=dev) if tracking != abi.TRACKING["none"] else None
+        gain = torch.empty((nrows, nb), dtype=torch.float32, device=dev) if nb > 1 else None
+        opt = lambda x: None if x is None else _ptr(x)
+        table = (C.c_void_p * nb)(*[r.data_ptr() if n else None for r in rows])
+        check(self.lib, self.lib.ofdm_receive_stream_diversity(
+            self.ctx, table, nb, n, C.byref(opts), C.byref(sopts), timing, tracking, abi.PAYLOAD[payload], max_packets,
+            _ptr(pk), _ptr(cnt), opt(words), opt(eq), opt(counters), opt(metric), opt(cross), opt(tim), opt(ph), opt(gain)),
+              "receive_stream_diversity")
+        return pk, cnt, words, eq, metric, cross, tim, ph, gain
+
     def impair_stream(self, x, power: float, snr_db: float, cfo_hz: float = 0.0, taps=None, noise: str = "real",
                       seed: int = 0x80211A, trial: int = 0, snr_index: int = 0, index0: int = 0, lead: int = 0,
                       out=None):

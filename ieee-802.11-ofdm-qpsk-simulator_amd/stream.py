@@ -8,7 +8,8 @@ d_bits and ofdm_transmit_packets' d_words use; transmit_main() is `python ofdm_p
 the executable specification of ofdm_score_packets (include/ofdm_mi355x_channel.h).  detection_metric() and
 positions() are the executable specification of the two detectors of include/ofdm_mi355x_detect.h, refine_timing() that
 of the fine timing of include/ofdm_mi355x_timing.h and track_pilots() that of the pilot phase tracking of
-include/ofdm_mi355x_track.h.
+include/ofdm_mi355x_track.h; diversity_metric(), refine_timing_branches() and combine_branches() are those of the
+receive diversity of include/ofdm_mi355x_diversity.h.
 """
 from __future__ import annotations
 
@@ -212,6 +213,147 @@ def slice_bits(z) -> np.ndarray:
     return np.stack([~pi, pr ^ pi], axis=-1).astype(np.int32).reshape(*z.shape[:-1], 2 * z.shape[-1])
 
 
+MAX_BRANCHES = 4          # OFDM_DIVERSITY_MAX_BRANCHES
+# the long training tones L_k in the reference's bin order (OFDM.c:494; ltf_sign, csrc/ofdm_device.h): +-1 on the 52
+# used bins 6..58, 0 at bin 32 and outside
+LTF_SIGNS = np.array([0] * 6 + [1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 1, 1, -1, -1, 1, 1, -1, 1, -1, 1, 1, 1, 1, 0,
+                                1, -1, -1, 1, 1, -1, 1, -1, 1, -1, -1, -1, -1, -1, 1, 1, -1, -1, 1, -1, 1, -1, 1, 1, 1, 1]
+                     + [0] * 5, np.float64)
+USED_BINS = tuple(int(b) for b in np.nonzero(LTF_SIGNS)[0])      # the 48 data bins and the 4 pilots
+SAMPLE_TIME = 1.0 / 20e6  # the frame's sample time after the matched filter's down-sampling (OFDM.c:16-17)
+
+
+def fft64(x) -> np.ndarray:
+    """The reference's transform convention (OFDM.c fft): DFT(x (-1)^n) over the last axis of 64 samples, so that bin 32
+    is the carrier and bins 6..58 are the used subcarriers in ascending frequency."""
+    x = np.asarray(x).astype(np.complex128)
+    if x.shape[-1] != 64:
+        raise ValueError(f"64 samples expected along the last axis, got {x.shape}")
+    return np.fft.fft(x * (1.0 - 2.0 * (np.arange(64) & 1)), axis=-1)
+
+
+def _branches(xs) -> np.ndarray:
+    """B recordings of one length as complex128 [B, n]; ValueError unless 1 <= B <= MAX_BRANCHES"""
+    rows = [np.asarray(x).astype(np.complex128).reshape(-1) for x in xs]
+    if not 1 <= len(rows) <= MAX_BRANCHES:
+        raise ValueError(f"1 to {MAX_BRANCHES} branches expected, got {len(rows)}")
+    if len({len(r) for r in rows}) != 1:
+        raise ValueError(f"branches of one length expected, got {[len(r) for r in rows]}")
+    return np.stack(rows)
+
+
+def diversity_metric(xs) -> np.ndarray:
+    """The combined detection metric of include/ofdm_mi355x_diversity.h in double precision, over B recordings xs of
+    one length n: with c_b and p_b the sums of the conjugate rule (detection_metric) on branch b,
+        c[i] = sum_b c_b[i],  p[i] = sum_b p_b[i],  M[i] = |c[i]|^2 / p[i]^2,  0 <= i < n - 63,
+    NaN where the power is zero (no crossing).  |c_b| does not see the phase of branch b's channel or a carrier
+    offset, and c_b's own phase is that of the common offset alone, so the branches add coherently.
+    diversity_metric([x]) is detection_metric(x, "conjugate"), bit for bit; select_packets(M, thr) is the rest."""
+    x = _branches(xs)
+    lc = positions(x.shape[1], "conjugate")
+    if lc == 0:
+        return np.zeros(0, np.float64)
+    c = np.zeros(lc, np.complex128)
+    p = np.zeros(lc, np.float64)
+    for r in x:
+        prod = r[:-32] * np.conj(r[32:])
+        c = c + np.lib.stride_tricks.sliding_window_view(prod, 32)[:lc].sum(axis=1)
+        p = p + np.lib.stride_tricks.sliding_window_view((r.real ** 2 + r.imag ** 2)[32:], 32)[:lc].sum(axis=1)
+    with np.errstate(all="ignore"):
+        return (c.real ** 2 + c.imag ** 2) / (p * p)
+
+
+def refine_timing_branches(xs, positions, template) -> dict:
+    """refine_timing over B recordings xs (include/ofdm_mi355x_diversity.h): L[j] = sum_b L_b[j] over the same 64
+    candidates, the largest L with the smallest j wins, and
+        quality = L[j*] / sum_b sum_s (sum_k |t[32 s + k]|^2 sum_k |x_b[q* + 32 s + k]|^2).
+    The window rule, the arguments and the result are refine_timing's; with one branch it is refine_timing."""
+    x = _branches(xs)
+    t = np.asarray(template).astype(np.complex128).reshape(-1)
+    if len(t) != 256:
+        raise ValueError(f"a template of 256 samples expected (ltf_template), got {len(t)}")
+    coarse = np.asarray(positions, np.int64).reshape(-1)
+    n, m = x.shape[1], len(coarse)
+    pos, shift = coarse.copy(), np.zeros(m, np.int32)
+    quality, metric = np.zeros(m, np.float64), np.zeros((m, TIMING_CANDIDATES), np.float64)
+    tc = np.conj(t).reshape(8, TIMING_SEGMENT)
+    te = (np.abs(t) ** 2).reshape(8, TIMING_SEGMENT).sum(axis=1)
+    for i, p in enumerate(coarse):
+        p = int(p)
+        if p + TIMING_FIRST < 0 or p + TIMING_SPAN >= n:
+            continue
+        wins = [np.lib.stride_tricks.sliding_window_view(r[p + TIMING_FIRST:p + TIMING_SPAN + 1], 256) for r in x]
+        lam = np.zeros(TIMING_CANDIDATES, np.float64)
+        for win in wins:
+            seg = (win.reshape(TIMING_CANDIDATES, 8, TIMING_SEGMENT) * tc).sum(axis=2)
+            lam = lam + (seg.real ** 2 + seg.imag ** 2).sum(axis=1)
+        metric[i] = lam
+        j = int(np.argmax(lam))
+        if not lam[j] > 0.0:
+            continue
+        den = sum(float((te * (np.abs(win[j]) ** 2).reshape(8, TIMING_SEGMENT).sum(axis=1)).sum()) for win in wins)
+        pos[i] = p - TIMING_BACK + j
+        shift[i] = j - TIMING_BACK
+        quality[i] = lam[j] / den
+    return dict(positions=pos, coarse=coarse, shift=shift, quality=quality, metric=metric)
+
+
+def _rotate(frames, f_hz: float) -> np.ndarray:
+    """frame sample i times exp(-j 2 pi f Ts i) (OFDM.c:802,825)"""
+    return frames * np.exp(-2j * np.pi * f_hz * SAMPLE_TIME * np.arange(frames.shape[-1]))
+
+
+def combine_branches(frames, tracking: str = "none", float_cfo: bool = True) -> dict:
+    """The diversity decode rule of include/ofdm_mi355x_diversity.h in double precision, its executable specification.
+    frames: complex [B, 320 + 80 D], every branch's matched-filtered frame at the packet's position (the oracle's
+    rxframe dump); one-dimensional input is one branch.
+        coarse CFO  fc = -angle(sum_b sum_{k<16} f_b[80 + k] conj(f_b[96 + k])) / (2 pi 16 Ts)
+        fine CFO    ff = -angle(sum_b sum_{k<64} g_b[192 + k] conj(g_b[256 + k])) / (2 pi 64 Ts), g_b = f_b rotated by fc
+                    (float_cfo: each rounded to fp32 as it is formed, the C receiver's)
+        rotation    every branch by fc + ff
+        spectra     S_b = fft64(LTF1 + LTF2), H_b = LTF_SIGNS S_b / 2, Y_{b,d} = fft64 of data symbol d past its prefix
+        combining   N_d[k] = sum_b Y_{b,d}[k] conj(H_b[k]),  G[k] = sum_b |H_b[k]|^2,  z_d = N_d / G on the 48 data bins
+        tracking    "pilots": P_d = sum_pilots p_k N_d[k]; u_d, the fallback and z' = z conj(u_d) as track_pilots
+        gain        gain[b] = sum over the 52 used bins of |H_b[k]|^2 / 52
+    With one branch H, Y and z are the reference's own (the oracle's H, Yf and nopilot dumps).
+
+    Returns z (complex128 [D, 48]: z, or z' with tracking), N ([D, 64]), G ([64]), H ([B, 64]), Y ([B, D, 64]), gain
+    ([B]), cfo (fc, ff), and with tracking u, phase, P and fallback ([D]) as track_pilots gives them (else None)."""
+    if tracking not in TRACKINGS:
+        raise ValueError(f"tracking must be one of {TRACKINGS}, got {tracking!r}")
+    f = np.asarray(frames).astype(np.complex128)
+    f = f.reshape(1, -1) if f.ndim == 1 else f
+    nfr = f.shape[-1]
+    if f.ndim != 2 or not 1 <= len(f) <= MAX_BRANCHES or nfr < 400 or (nfr - 320) % 80:
+        raise ValueError(f"frames [B, 320 + 80 D] with 1 <= B <= {MAX_BRANCHES} expected, got {f.shape}")
+    d = (nfr - 320) // 80
+    rnd = (lambda v: float(np.float32(v))) if float_cfo else float
+    with np.errstate(all="ignore"):
+        pp = (f[:, 80:96] * np.conj(f[:, 96:112])).sum()
+        fc = rnd(-np.arctan2(pp.imag, pp.real) / (2 * np.pi * 16 * SAMPLE_TIME))
+        g = _rotate(f, fc)
+        pp = (g[:, 192:256] * np.conj(g[:, 256:320])).sum()
+        ff = rnd(-np.arctan2(pp.imag, pp.real) / (2 * np.pi * 64 * SAMPLE_TIME))
+        r = _rotate(f, fc + ff)
+        H = LTF_SIGNS * fft64(r[:, 192:256] + r[:, 256:320]) / 2
+        Y = fft64(np.stack([r[:, 336 + 80 * s:400 + 80 * s] for s in range(d)], axis=1))       # [B, D, 64]
+        N = (Y * np.conj(H)[:, None, :]).sum(axis=0)
+        G = (np.abs(H) ** 2).sum(axis=0)
+        db = list(DATA_BINS)
+        z = N[:, db] / G[db]
+        gain = (np.abs(H[:, list(USED_BINS)]) ** 2).sum(axis=1) / len(USED_BINS)
+        out = dict(z=z, N=N, G=G, H=H, Y=Y, gain=gain, cfo=(fc, ff), u=None, phase=None, P=None, fallback=None)
+        if tracking == "pilots":
+            # track_pilots on (N, G): P_d = sum p_k N_d[k] conj(G[k]) would weigh the pilots by G, so the rule is spelt out
+            P = (np.asarray(PILOT_VALUES) * N[:, list(PILOT_BINS)]).sum(axis=1)
+            mag = np.abs(P)
+            fallback = ~(np.isfinite(P.real) & np.isfinite(P.imag) & np.isfinite(mag) & (mag > 0))
+            u = np.where(fallback, 1.0 + 0.0j, P / np.where(fallback, 1.0, mag))
+            phase = np.where(fallback, 0.0, np.angle(np.where(fallback, 1.0, P)))
+            out.update(z=np.where(fallback[:, None], z, z * np.conj(u)[:, None]), u=u, phase=phase, P=P, fallback=fallback)
+    return out
+
+
 def first_packet(sel: dict) -> int:
     """Packet_Selection's answer from select_packets': the first packet that is not the last front's, 0 when none."""
     keep = sel["positions"][sel["flags"] & LAST_FRONT == 0]
@@ -402,6 +544,7 @@ def main(argv=None) -> int:
     return 0
 
 
-__all__ = ["track_pilots", "slice_bits", "TRACKINGS", "PILOT_BINS", "PILOT_VALUES", "DATA_BINS", "ltf_template", "refine_timing", "TIMINGS", "LTF_START", "TIMING_BACK", "TIMING_FWD", "TIMING_CANDIDATES", "TIMING_FIRST", "TIMING_SPAN",
+__all__ = ["diversity_metric", "refine_timing_branches", "combine_branches", "fft64", "LTF_SIGNS", "USED_BINS", "MAX_BRANCHES", "SAMPLE_TIME",
+           "track_pilots", "slice_bits", "TRACKINGS", "PILOT_BINS", "PILOT_VALUES", "DATA_BINS", "ltf_template", "refine_timing", "TIMINGS", "LTF_START", "TIMING_BACK", "TIMING_FWD", "TIMING_CANDIDATES", "TIMING_FIRST", "TIMING_SPAN",
            "select_packets", "detection_metric", "positions", "DETECTORS", "unpack_cross", "first_packet", "synthetic_segments", "main", "pack_messages",
            "transmit_main", "score_packets", "SCORE_MAX_WINDOW", "NSCORE", "MAX_DATA_SYMBOLS", "THRESHOLD", "FRONT_GAP", "CONFIRM", "PACKET_OFFSET", "LAST_FRONT"]

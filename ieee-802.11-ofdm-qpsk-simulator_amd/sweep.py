@@ -176,7 +176,7 @@ def captures_main(argv=None):
 def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: float = 0.0, taps=None,
                noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=None, fading=None,
                detector: str = "reference", threshold: float = 0.75, timing: str = "none",
-               tracking: str = "none") -> dict:
+               tracking: str = "none", branches: int = 1) -> dict:
     """Packet-error and bit-error counts against SNR for packets that each carry their own bits, the recording never
     leaving the device: the packets (words: uint32 [n, 3 n_data], each behind `gap` idle samples, and a closing gap)
     are transmitted once; per SNR point q the clean recording is impaired into a second buffer with the noise stream
@@ -200,6 +200,11 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     right one.
     tracking: "none", or "pilots": every data symbol is turned back by its four pilots' common phase before the slicer
     (include/ofdm_mi355x_track.h).  For long packets; on 2-symbol packets it costs a little BER.
+    branches: B = 1..4 receive antennas (include/ofdm_mi355x_diversity.h).  Branch b carries the same
+    packets, through taps of its own when fading (Engine.draw_taps at index0 + b n), under the noise stream
+    (seed, trial B + b, q); the B recordings are received together (Engine.receive_diversity_device).  power is then the
+    mean of the branches' realised powers, and every branch gets the noise power it sets.  B > 1 needs
+    detector="conjugate"; with B = 1 every call and every total is what it was without the argument.
 
     Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
     import torch  # noqa: PLC0415
@@ -207,6 +212,10 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     n, plen = int(len(words)), abi.packet_len(n_data)
     abi.timing_code(timing)                                          # ValueError before anything is set or launched
     abi.tracking_code(tracking)
+    if isinstance(branches, bool) or not isinstance(branches, int) or not 1 <= branches <= abi.DIVERSITY_MAX_BRANCHES:
+        raise ValueError(f"branches must be an integer in [1, {abi.DIVERSITY_MAX_BRANCHES}], got {branches!r}")
+    if branches > 1 and detector != "conjugate":
+        raise ValueError(f"branches={branches} needs detector='conjugate', got {detector!r}")
     pdp = None
     if fading is not None:
         if set(fading) - {"pdp", "index0"} or "pdp" not in fading:
@@ -223,23 +232,32 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     set_message(engine, " " * (12 * n_data))
     dev = torch.device("cuda", engine.device)
     w = words if torch.is_tensor(words) else torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(dev)
+    nb = branches
     if pdp is None:
         stride = plen + gap
         n_out = n * stride + gap
-        clean = engine.transmit_packets(w, n_data, pos0=gap, stride=stride, n_out=n_out)
+        clean = [engine.transmit_packets(w, n_data, pos0=gap, stride=stride, n_out=n_out)] * nb
     else:
         stride = abi.faded_len(n_data, len(pdp)) + gap
         n_out = n * stride + gap
-        h = engine.draw_taps(n, pdp, seed=seed, index0=fading.get("index0", 0))
-        clean = engine.transmit_faded(w, n_data, h, pos0=gap, stride=stride, n_out=n_out)
+        clean = []
+        for b in range(nb):
+            h = engine.draw_taps(n, pdp, seed=seed, index0=fading.get("index0", 0) + b * n)
+            clean.append(engine.transmit_faded(w, n_data, h, pos0=gap, stride=stride, n_out=n_out))
     # mean |w|^2 over the packets' samples: the gaps are zero
-    power = float((clean.real.double() ** 2 + clean.imag.double() ** 2).sum()) / max(n * plen, 1)
-    rec = torch.empty_like(clean)
+    # (unfaded branches share one clean recording; faded ones have a realised power each, and the sweep takes their mean)
+    powers = [float((c.real.double() ** 2 + c.imag.double() ** 2).sum()) / max(n * plen, 1) for c in (clean if pdp is not None else clean[:1])]
+    power = powers[0] if nb == 1 else float(np.mean(powers))
+    rec = [torch.empty_like(clean[0]) for _ in range(nb)]
     totals = torch.zeros((len(snr), abi.NSCORE), dtype=torch.int64, device=dev)
     for q, s in enumerate(snr):
-        engine.impair_stream(clean, power, float(s), cfo_hz, taps=taps, noise=noise, seed=seed, trial=trial,
-                             snr_index=q, out=rec)
-        rx = engine.receive_stream_device(rec, detector=detector, threshold=threshold, timing=timing, tracking=tracking)
+        for b in range(nb):
+            engine.impair_stream(clean[b], power, float(s), cfo_hz, taps=taps, noise=noise, seed=seed, trial=trial * nb + b,
+                                 snr_index=q, out=rec[b])
+        if nb == 1:
+            rx = engine.receive_stream_device(rec[0], detector=detector, threshold=threshold, timing=timing, tracking=tracking)
+        else:
+            rx = engine.receive_diversity_device(rec, detector=detector, threshold=threshold, timing=timing, tracking=tracking)
         engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])
     return dict(snr_db=snr, totals=totals.cpu().numpy(), power=power, packets=n, samples=n_out)
 
@@ -289,10 +307,17 @@ def link_main(argv=None) -> int:
     ap.add_argument("--tracking", choices=tuple(abi.TRACKING), default="none",
                     help="pilots: turn every data symbol back by its four pilots' common phase before the slicer "
                          "(for long packets; costs a little BER on 2-symbol packets)")
+    ap.add_argument("--branches", type=int, default=1,
+                    help=f"receive antennas, 1 to {abi.DIVERSITY_MAX_BRANCHES}: independently faded and independently noisy "
+                         "recordings of the same packets, combined in the receiver (more than 1 needs --detector conjugate)")
     ap.add_argument("--out", default="data")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:
         raise SystemExit("--threshold must be inside (0, 1)")
+    if not 1 <= a.branches <= abi.DIVERSITY_MAX_BRANCHES:
+        raise SystemExit(f"--branches must be in [1, {abi.DIVERSITY_MAX_BRANCHES}]")
+    if a.branches > 1 and a.detector != "conjugate":
+        raise SystemExit("--branches above 1 needs --detector conjugate")
     snr = parse_snr_grid(a.snr)
     fading = None
     if a.fading or a.pdp:
@@ -315,7 +340,7 @@ def link_main(argv=None) -> int:
     with Engine(0) as eng:
         res = link_sweep(eng, words, d, a.gap, snr, cfo_hz=a.cfo_hz, taps=None if a.taps is None else parse_taps(a.taps),
                          noise=a.noise, seed=a.seed, fading=fading, detector=a.detector, threshold=a.threshold,
-                         timing=a.timing, tracking=a.tracking)
+                         timing=a.timing, tracking=a.tracking, branches=a.branches)
     wall = time.perf_counter() - t0
     t = res["totals"]
     ber = t[:, abi.S_BIT_ERR] / np.maximum(t[:, abi.S_BITS], 1)
