@@ -186,6 +186,38 @@ _DIVERSITY_SIGS = {
 DIVERSITY_FUNCTIONS = tuple(_DIVERSITY_SIGS)
 DIVERSITY_MAX_BRANCHES = 4                       # OFDM_DIVERSITY_MAX_BRANCHES
 
+# the extension header include/ofdm_mi355x_code.h (the coded link: K = 7 rate-1/2 encoder over the payload words, the
+# per-subcarrier gains of received records and a CSI-weighted soft Viterbi decoder over d_eq); the export lists above and
+# ABI_VERSION do not change with it
+CODE_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_code.h"
+_CODE_SIGS = {
+    "ofdm_code_encode": (C.c_int, [_V, C.c_int32, _V, C.c_int64, _V]),
+    "ofdm_stream_csi": (C.c_int, [_V, C.POINTER(_V), C.c_int32, C.c_int64, _V, _V, C.c_int64, _V]),
+    "ofdm_code_decode": (C.c_int, [_V, C.c_int32, _V, _V, _V, C.c_int64, _V, _V]),
+}
+CODE_FUNCTIONS = tuple(_CODE_SIGS)
+K_CODE_ENCODE, K_STREAM_CSI, K_CODE_DECODE = 18, 19, 20      # OFDM_K_CODE_ENCODE, OFDM_K_STREAM_CSI, OFDM_K_CODE_DECODE
+CODE_TAIL_BITS = 6                               # OFDM_CODE_TAIL_BITS
+
+
+def code_info_bits(n_data: int) -> int:
+    """OFDM_CODE_INFO_BITS: 48 D - 6"""
+    return 48 * int(n_data) - CODE_TAIL_BITS
+
+
+def code_info_words(n_data: int) -> int:
+    """OFDM_CODE_INFO_WORDS: ceil((48 D - 6) / 32)"""
+    return (code_info_bits(n_data) + 31) // 32
+
+
+CODE_DECODE_WAVES = 4                            # CDEC_WAVES (csrc/ofdm_code.hip): rows per block and sweep
+
+
+def code_decode_lds_bytes(n_data: int) -> int:
+    """The decode kernel's dynamic LDS per block: per wave 96 D floats (the soft values) and 48 D 64-bit words (the
+    decisions), 11.25 KiB at D = 15; it has no static LDS."""
+    return CODE_DECODE_WAVES * (96 * int(n_data) * 4 + 48 * int(n_data) * 8)
+
 
 class OfdmError(RuntimeError):
     pass
@@ -404,7 +436,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib = C.CDLL(str(p))
     for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS,
                               **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS, **_TIMING_SIGS, **_TRACK_SIGS,
-                              **_DIVERSITY_SIGS}.items():
+                              **_DIVERSITY_SIGS, **_CODE_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -51,11 +51,12 @@ struct Ctx {
     // ofdm_mi355x_fading.h), 12: the stream receiver's conjugate-correlation detector (OFDM_K_STREAM_DETECT_CONJ of
     // ofdm_mi355x_detect.h), 13: its fine timing kernel (OFDM_K_STREAM_TIMING of ofdm_mi355x_timing.h), 14: its pilot-tracking
     // decode (OFDM_K_STREAM_DECODE_TRACK of ofdm_mi355x_track.h), 15..17: the diversity receiver's detection, timing and
-    // decode (OFDM_K_STREAM_*_DIV of ofdm_mi355x_diversity.h), added at the tail
+    // decode (OFDM_K_STREAM_*_DIV of ofdm_mi355x_diversity.h), 18..20: the coded link's encoder, gains and Viterbi
+    // decoder (OFDM_K_CODE_ENCODE, OFDM_K_STREAM_CSI, OFDM_K_CODE_DECODE of ofdm_mi355x_code.h), added at the tail
     enum { K_FFT = 0, K_TX = 1, K_RX = 2, K_FRAME = 3, K_STREAM_DETECT = 4, K_STREAM_SELECT = 5, K_STREAM_DECODE = 6,
            K_TRANSMIT = 7, K_CHANNEL = 8, K_SCORE = 9, K_FADE = 10, K_DRAW_TAPS = 11, K_STREAM_DETECT_CONJ = 12,
            K_STREAM_TIMING = 13, K_STREAM_DECODE_TRACK = 14, K_STREAM_DETECT_DIV = 15, K_STREAM_TIMING_DIV = 16,
-           K_STREAM_DECODE_DIV = 17, NK = 18 };
+           K_STREAM_DECODE_DIV = 17, K_CODE_ENCODE = 18, K_STREAM_CSI = 19, K_CODE_DECODE = 20, NK = 21 };
     int device = 0;
     int cus = 256;
     hipStream_t own = nullptr;       // created by the context

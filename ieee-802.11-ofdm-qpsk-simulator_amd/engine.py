@@ -563,13 +563,14 @@ class Engine:
 
     def receive_stream_device(self, samples, mode: str = "c", payload: str = "message", max_packets: int | None = None,
                               counters=None, detector: str = "reference", threshold: float = 0.75,
-                              timing: str = "none", tracking: str = "none") -> dict:
+                              timing: str = "none", tracking: str = "none", want_eq: bool = False) -> dict:
         """receive_stream for a device recording without the read-back: nothing waits for the device.  samples: a
         one-dimensional contiguous torch complex64 tensor on this engine's device.  Returns d_packets (uint8
         [rows, 64], ofdm_stream_packet), d_count (int64 [2]: found, written) and d_words (int32 [rows, 3 D]), of which
         the first d_count[1] rows are written, and frames -- what score_packets takes.  detector, threshold: as
         receive_stream's.  timing: as receive_stream's; d_timing (uint8 [rows, 16], ofdm_stream_timing) with "ltf" or "ltf-matlab", else
-        None.  tracking: as receive_stream's; d_phase (float32 [rows, D]) with "pilots", else None."""
+        None.  tracking: as receive_stream's; d_phase (float32 [rows, D]) with "pilots", else None.  want_eq: the
+        result also holds d_eq (complex64 [rows, 48 D], the equalised subcarriers), what decode_coded takes."""
         torch = _torch()
         opts = make_rx_opts(mode)
         nd = self.payload_frames(payload)
@@ -586,9 +587,12 @@ class Engine:
         if int(max_packets) != max_packets or max_packets < 0:
             raise ValueError(f"max_packets must be a non-negative integer, got {max_packets!r}")
         sopts = abi.make_stream_opts(detector, threshold)
-        out = self._launch_receive_stream(samples, opts, payload, nd, int(max_packets), True, False, False, False,
+        out = self._launch_receive_stream(samples, opts, payload, nd, int(max_packets), True, bool(want_eq), False, False,
                                           counters, sopts, abi.timing_code(timing), abi.tracking_code(tracking))
-        return dict(d_packets=out[0], d_count=out[1], d_words=out[2], frames=nd, d_timing=out[6], d_phase=out[7])
+        res = dict(d_packets=out[0], d_count=out[1], d_words=out[2], frames=nd, d_timing=out[6], d_phase=out[7])
+        if want_eq:
+            res.update(d_eq=out[3])
+        return res
 
     def _launch_receive_stream(self, t, opts, payload, nd, max_packets, want_bits, want_eq, want_metric, want_cross,
                                counters, sopts=None, timing=0, tracking=0):
@@ -741,10 +745,11 @@ class Engine:
 
     def receive_diversity_device(self, branches, mode: str = "c", payload: str = "message",
                                  max_packets: int | None = None, counters=None, detector: str = "reference",
-                                 threshold: float = 0.75, timing: str = "none", tracking: str = "none") -> dict:
+                                 threshold: float = 0.75, timing: str = "none", tracking: str = "none",
+                                 want_eq: bool = False) -> dict:
         """receive_diversity for device recordings without the read-back: nothing waits for the device.  Returns what
         receive_stream_device returns -- d_packets, d_count, d_words, frames, d_timing, d_phase -- and d_gain (float32
-        [rows, B], None for B = 1)."""
+        [rows, B], None for B = 1); with want_eq also d_eq (complex64 [rows, 48 D])."""
         opts = make_rx_opts(mode)
         nd = self.payload_frames(payload)
         if isinstance(branches, np.ndarray):
@@ -755,10 +760,96 @@ class Engine:
         tcode, kcode = abi.timing_code(timing), abi.tracking_code(tracking)
         if len(rows) > 1 and detector != "conjugate":
             raise ValueError(f"{len(rows)} branches need detector='conjugate', got {detector!r}")
-        out = self._launch_receive_diversity(rows, opts, payload, nd, max_packets, True, False, False, False, counters,
+        out = self._launch_receive_diversity(rows, opts, payload, nd, max_packets, True, bool(want_eq), False, False, counters,
                                              sopts, tcode, kcode)
-        return dict(d_packets=out[0], d_count=out[1], d_words=out[2], frames=nd, d_timing=out[6], d_phase=out[7],
-                    d_gain=out[8])
+        res = dict(d_packets=out[0], d_count=out[1], d_words=out[2], frames=nd, d_timing=out[6], d_phase=out[7],
+                   d_gain=out[8])
+        if want_eq:
+            res.update(d_eq=out[3])
+        return res
+
+    # ---- the coded link (include/ofdm_mi355x_code.h) ------------------------------------
+    def encode_packets(self, info, n_data: int):
+        """Information words -> payload words on the device (ofdm_code_encode; stream.conv_encode is the rule): the
+        K = 7 rate-1/2 code, the per-symbol interleaver and the precoding for the reference's QPSK map.  info: uint32
+        or int32 [n, W_i] (abi.code_info_words(n_data)), a numpy array (uploaded) or a contiguous tensor on this engine's
+        device.  Returns an int32 device tensor [n, 3 n_data], what transmit_packets and transmit_faded take."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        nd = int(n_data)
+        if nd != n_data or not 1 <= nd <= abi.LONG_MAX_DATA_SYMBOLS:
+            raise ValueError(f"n_data must be in [1, {abi.LONG_MAX_DATA_SYMBOLS}], got {n_data!r}")
+        wi = abi.code_info_words(nd)
+        if isinstance(info, np.ndarray):
+            if info.dtype not in (np.uint32, np.int32) or info.ndim != 2:
+                raise ValueError(f"info must be uint32 [n, {wi}], got {info.dtype} {info.shape}")
+            info = torch.from_numpy(np.ascontiguousarray(info).view(np.int32)).to(dev)
+        if not torch.is_tensor(info) or info.dtype != torch.int32 or info.dim() != 2 or info.shape[1] != wi:
+            raise ValueError(f"info must be 32-bit integers [n, {wi}] for {nd} data symbols")
+        if info.device != dev or not info.is_contiguous():
+            raise ValueError(f"info must be contiguous on {dev}")
+        n = int(info.shape[0])
+        words = torch.empty((n, 3 * nd), dtype=torch.int32, device=dev)
+        if n:
+            check(self.lib, self.lib.ofdm_code_encode(self.ctx, nd, _ptr(info), n, _ptr(words)), "code_encode")
+        return words
+
+    def stream_csi(self, branches_or_samples, rx: dict):
+        """The per-subcarrier gains of the records of a finished receive call (ofdm_stream_csi; stream.channel_gain is
+        the rule): csi[i][m] = sum over the branches of |H_b|^2 at data subcarrier m, d_eq's order.
+        branches_or_samples: the recording the call ran on, a one-dimensional complex64 device tensor, or its branches
+        as receive_diversity takes them.  rx: the call's result with d_packets and d_count (receive_stream_device,
+        receive_diversity_device, or receive_stream(keep_device=True)).  Returns a float32 device tensor [rows, 48] of
+        which the first d_count[1] rows are written.  Nothing waits for the device."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        if torch.is_tensor(branches_or_samples) and branches_or_samples.dim() == 1:
+            branches_or_samples = [branches_or_samples]
+        rows = self._branch_tensors(branches_or_samples)
+        nb, n = len(rows), int(rows[0].shape[0])
+        pk, cnt = rx["d_packets"], rx["d_count"]
+        max_packets = int(pk.shape[0])
+        csi = torch.empty((max_packets, 48), dtype=torch.float32, device=dev)
+        table = (C.c_void_p * nb)(*[r.data_ptr() if n else None for r in rows])
+        check(self.lib, self.lib.ofdm_stream_csi(self.ctx, table, nb, n, _ptr(pk), _ptr(cnt), max_packets, _ptr(csi)),
+              "stream_csi")
+        return csi
+
+    def decode_coded(self, rx, csi=None, want_path: bool = False, n_data: int | None = None) -> dict:
+        """The soft Viterbi decoder over equalised subcarriers (ofdm_code_decode; stream.conv_soft and
+        stream.viterbi_decode are the rule, bit for bit).  rx: a receive call's result with d_eq and d_count
+        (want_eq=True), or a complex64 device tensor [n, 48 D] to decode whole.  csi: stream_csi's tensor, or None for
+        unweighted soft values.  Returns d_info (int32 [rows, W_i], MSB first; with rx a result, the first d_count[1]
+        rows are written) and d_path (float32 [rows], the path metric; None without want_path).  Nothing waits for the
+        device."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        if isinstance(rx, dict):
+            eq, cnt = rx.get("d_eq"), rx["d_count"]
+            if eq is None:
+                raise ValueError("the receive call must be made with want_eq=True")
+        else:
+            eq, cnt = rx, None
+        if not torch.is_tensor(eq) or eq.dtype != torch.complex64 or eq.dim() != 2 or eq.shape[1] % 48:
+            raise ValueError("d_eq must be a complex64 tensor [n, 48 D]")
+        if eq.device != dev or not eq.is_contiguous():
+            raise ValueError(f"d_eq must be contiguous on {dev}")
+        n, nd = int(eq.shape[0]), int(eq.shape[1]) // 48
+        if n_data is not None and int(n_data) != nd:
+            raise ValueError(f"d_eq holds {nd} data symbols per row, n_data is {n_data}")
+        if not 1 <= nd <= abi.LONG_MAX_DATA_SYMBOLS:
+            raise ValueError(f"1 to {abi.LONG_MAX_DATA_SYMBOLS} data symbols per row expected, got {nd}")
+        if csi is not None:
+            if not (torch.is_tensor(csi) and csi.dtype == torch.float32 and csi.device == dev and csi.is_contiguous()
+                    and tuple(csi.shape) == (n, 48)):
+                raise ValueError(f"csi must be a contiguous float32 device tensor [{n}, 48]")
+        info = torch.empty((n, abi.code_info_words(nd)), dtype=torch.int32, device=dev)
+        path = torch.empty(n, dtype=torch.float32, device=dev) if want_path else None
+        opt = lambda x: None if x is None else _ptr(x)
+        if n:
+            check(self.lib, self.lib.ofdm_code_decode(self.ctx, nd, _ptr(eq), opt(csi), opt(cnt), n, _ptr(info), opt(path)),
+                  "code_decode")
+        return dict(d_info=info, d_path=path, frames=nd)
 
     @staticmethod
     def _div_max_packets(n: int, max_packets) -> int:

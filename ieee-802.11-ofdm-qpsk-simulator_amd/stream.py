@@ -9,7 +9,8 @@ the executable specification of ofdm_score_packets (include/ofdm_mi355x_channel.
 positions() are the executable specification of the two detectors of include/ofdm_mi355x_detect.h, refine_timing() that
 of the fine timing of include/ofdm_mi355x_timing.h and track_pilots() that of the pilot phase tracking of
 include/ofdm_mi355x_track.h; diversity_metric(), refine_timing_branches() and combine_branches() are those of the
-receive diversity of include/ofdm_mi355x_diversity.h.
+receive diversity of include/ofdm_mi355x_diversity.h; conv_encode(), conv_soft(), viterbi_decode() and channel_gain()
+those of the coded link of include/ofdm_mi355x_code.h.
 """
 from __future__ import annotations
 
@@ -335,7 +336,7 @@ def combine_branches(frames, tracking: str = "none", float_cfo: bool = True) -> 
         pp = (g[:, 192:256] * np.conj(g[:, 256:320])).sum()
         ff = rnd(-np.arctan2(pp.imag, pp.real) / (2 * np.pi * 64 * SAMPLE_TIME))
         r = _rotate(f, fc + ff)
-        H = LTF_SIGNS * fft64(r[:, 192:256] + r[:, 256:320]) / 2
+        H = _channel(r)
         Y = fft64(np.stack([r[:, 336 + 80 * s:400 + 80 * s] for s in range(d)], axis=1))       # [B, D, 64]
         N = (Y * np.conj(H)[:, None, :]).sum(axis=0)
         G = (np.abs(H) ** 2).sum(axis=0)
@@ -430,6 +431,232 @@ def score_packets(tx_pos, tx_words, rx_pos, rx_words, window=(8, 40)) -> dict:
     totals[:6] = (n_tx, int(hit.sum()), n_rx, 32 * tw.shape[1] * int(hit.sum()), int(bit_err.sum()),
                   int((bit_err > 0).sum()))
     return dict(rx_index=rx_index, bit_err=bit_err, totals=totals)
+
+
+# ---- the coded link (include/ofdm_mi355x_code.h): 802.11a's K = 7 rate-1/2 mother code over the payload words ----
+CODE_TAIL = 6             # zero tail bits: the trellis ends in state 0
+CODE_STATES = 64
+CODE_CLAMP = 2.0 ** 100   # |soft value| at most: 1,440 of them cannot overflow fp32
+# generators 133 and 171 (octal) over (u_t, u_t-1, .., u_t-6)
+CODE_TAPS_A = (0, 2, 3, 5, 6)
+CODE_TAPS_B = (0, 1, 2, 3, 6)
+
+
+def INFO_BITS(n_data: int) -> int:
+    """K_info = 48 D - 6 information bits of a packet of D data symbols"""
+    d = int(n_data)
+    if d != n_data or not 1 <= d <= MAX_DATA_SYMBOLS:
+        raise ValueError(f"n_data must be in [1, {MAX_DATA_SYMBOLS}], got {n_data!r}")
+    return 48 * d - CODE_TAIL
+
+
+def INFO_WORDS(n_data: int) -> int:
+    """W_i = ceil(K_info / 32) words of uint32 per packet, MSB first"""
+    return (INFO_BITS(n_data) + 31) // 32
+
+
+def pack_coded_messages(texts, n_data: int | None = None):
+    """Information words of one coded packet per text: (uint32 [n, W_i], D).  A text (str, latin-1, or bytes) fills the
+    first 8 len information bits, MSB first, and is padded with ' ' to the K_info // 8 whole characters a packet holds;
+    the few bits past them are 0.  D is n_data, or the smallest with 48 D - 6 >= 8 len for every text (at least 1).
+    ValueError for a text that needs more than 15 symbols or more than n_data."""
+    rows = [t.encode("latin-1") if isinstance(t, str) else bytes(t) for t in texts]
+    need = [max((8 * len(b) + CODE_TAIL + 47) // 48, 1) for b in rows]
+    for b, k in zip(rows, need):
+        if k > MAX_DATA_SYMBOLS:
+            raise ValueError(f"a text of {len(b)} characters needs {k} data symbols, a coded packet carries at most "
+                             f"{MAX_DATA_SYMBOLS} ({INFO_BITS(MAX_DATA_SYMBOLS) // 8} characters)")
+    d = max(need, default=1) if n_data is None else int(n_data)
+    if not 1 <= d <= MAX_DATA_SYMBOLS:
+        raise ValueError(f"n_data must be in [1, {MAX_DATA_SYMBOLS}], got {n_data!r}")
+    if need and max(need) > d:
+        raise ValueError(f"a text needs {max(need)} data symbols, n_data is {d}")
+    buf = np.zeros((len(rows), 4 * INFO_WORDS(d)), np.uint8)
+    buf[:, :INFO_BITS(d) // 8] = 0x20
+    for k, b in enumerate(rows):
+        buf[k, :len(b)] = np.frombuffer(b, np.uint8)
+    return buf.view(">u4").astype(np.uint32), d
+
+
+def interleave_index() -> np.ndarray:
+    """802.11a's first permutation for N_CBPS = 96 (the second is the identity for QPSK): coded bit k of a data symbol
+    goes to position j[k] = 6 (k mod 16) + k // 16"""
+    k = np.arange(96)
+    return 6 * (k % 16) + k // 16
+
+
+def _info_bits(info_words, n_data: int) -> np.ndarray:
+    """uint32 [n, W_i] -> uint8 [n, K_info], MSB first; the unused low bits of the last word are dropped"""
+    w = np.ascontiguousarray(np.asarray(info_words).astype(np.uint32, copy=False))
+    if w.ndim != 2 or w.shape[1] != INFO_WORDS(n_data):
+        raise ValueError(f"information words [n, {INFO_WORDS(n_data)}] expected for {n_data} data symbols, got {w.shape}")
+    return np.unpackbits(w.astype(">u4").view(np.uint8), axis=1)[:, :INFO_BITS(n_data)]
+
+
+def _pack_bits(bits) -> np.ndarray:
+    """uint8 [n, k] -> uint32 [n, ceil(k / 32)], MSB first, the last word's unused low bits 0"""
+    b = np.asarray(bits, np.uint8)
+    pad = (-b.shape[1]) % 32
+    b = np.concatenate([b, np.zeros((len(b), pad), np.uint8)], axis=1)
+    return np.ascontiguousarray(np.packbits(b, axis=1)).view(">u4").astype(np.uint32)
+
+
+def conv_code_bits(u) -> np.ndarray:
+    """The mother code on bit rows u [n, T] (u_t = 0 for t < 0): uint8 [n, 2 T], c[2 t] = A_t, c[2 t + 1] = B_t"""
+    u = np.asarray(u, np.uint8)
+    pad = np.concatenate([np.zeros((len(u), 6), np.uint8), u], axis=1)
+    t = u.shape[1]
+    a = np.zeros_like(u)
+    b = np.zeros_like(u)
+    for s in CODE_TAPS_A:
+        a ^= pad[:, 6 - s:6 - s + t]
+    for s in CODE_TAPS_B:
+        b ^= pad[:, 6 - s:6 - s + t]
+    return np.stack([a, b], axis=-1).reshape(len(u), 2 * t)
+
+
+def conv_encode(info_words, n_data: int, precode: bool = True) -> np.ndarray:
+    """The encoder of include/ofdm_mi355x_code.h, its executable specification: information words uint32 [n, W_i]
+    (MSB first) -> payload words uint32 [n, 3 D] for ofdm_transmit_packets.  K_info information bits and six zero tail
+    bits through the K = 7 rate-1/2 code (generators 133, 171 octal), each data symbol's 96 coded bits through
+    interleave_index(), and the interleaved bits g precoded for the reference's QPSK map: b[2 m] = g[2 m],
+    b[2 m + 1] = g[2 m] ^ g[2 m + 1], so that im > 0 iff g[2 m] = 0 and re > 0 iff g[2 m + 1] = 0.
+    precode=False feeds g to the map as it is (what the precoding is measured against, not a mode of the library)."""
+    u = _info_bits(info_words, n_data)
+    n = len(u)
+    u = np.concatenate([u, np.zeros((n, CODE_TAIL), np.uint8)], axis=1)
+    c = conv_code_bits(u).reshape(n, n_data, 96)
+    g = np.zeros_like(c)
+    g[:, :, interleave_index()] = c
+    if precode:
+        g = g.copy()
+        g[:, :, 1::2] ^= g[:, :, 0::2]
+    return _pack_bits(g.reshape(n, 96 * n_data))
+
+
+def conv_soft(eq, csi=None) -> np.ndarray:
+    """The soft values of include/ofdm_mi355x_code.h in trellis order: float32 [n, 96 D], the two of step t at 2 t and
+    2 t + 1.  eq: complex [n, 48 D] equalised subcarriers (d_eq); csi: [n, 48] gains (d_csi) or None for 1.  At
+    position j of data symbol d, subcarrier m = j >> 1: v = Im z for even j, Re z for odd j, z = eq[48 d + m];
+    lam = csi[m] v as one fp32 product; a non-finite lam is 0; |lam| is clamped to 2^100; positive means bit 0."""
+    z = np.asarray(eq).astype(np.complex64)
+    if z.ndim != 2 or z.shape[1] % 48 or not 1 <= z.shape[1] // 48 <= MAX_DATA_SYMBOLS:
+        raise ValueError(f"eq [n, 48 D] with 1 <= D <= {MAX_DATA_SYMBOLS} expected, got {z.shape}")
+    n, d = len(z), z.shape[1] // 48
+    v = np.stack([z.imag, z.real], axis=-1).reshape(n, d, 96)                 # position j = 2 m + (0: Im, 1: Re)
+    with np.errstate(all="ignore"):
+        if csi is not None:
+            w = np.asarray(csi).astype(np.float32)
+            if w.shape != (n, 48):
+                raise ValueError(f"csi [{n}, 48] expected, got {w.shape}")
+            v = v * np.repeat(w, 2, axis=1)[:, None, :]
+        v = v.astype(np.float32)
+        v = np.where(np.isfinite(v), v, np.float32(0))
+        v = np.clip(v, np.float32(-CODE_CLAMP), np.float32(CODE_CLAMP))
+    return np.ascontiguousarray(v[:, :, interleave_index()].reshape(n, 96 * d), np.float32)
+
+
+def _trellis():
+    """State s = u_t-1 << 5 | .. | u_t-6; the step's input u_t = s' >> 5 leads to s' = u_t << 5 | s >> 1, so the
+    predecessors of s' are p0 = (2 s') & 63 and p1 = p0 | 1 (u_t-6 = 0 and 1).  Returns p0 [64] and the coded bits
+    (A, B) on the branch p0 -> s' [64]; those on p1 -> s' are their complements (both generators tap u_t-6)."""
+    s = np.arange(CODE_STATES)
+    bit = lambda k: (s >> k) & 1                                     # u_t-i sits at bit 5 - i of s' for i = 0..5
+    a0 = bit(5) ^ bit(3) ^ bit(2) ^ bit(0)
+    b0 = bit(5) ^ bit(4) ^ bit(3) ^ bit(2)
+    return (2 * s) & 63, a0.astype(bool), b0.astype(bool)
+
+
+def viterbi_decode(soft) -> dict:
+    """The decoder of include/ofdm_mi355x_code.h in fp32, its executable specification, vectorised over packets.
+    soft: float32 [n, 96 D] in trellis order (conv_soft).  A Viterbi decoder over the 64 states with a correlation
+    metric that is maximised: M = 0 for state 0 and -inf for the others; per step and new state the two candidates
+    c_p = M[p] + ((+-lam[2 t]) + (+-lam[2 t + 1])), the sign "-" where the branch's coded bit is 1, the inner sum
+    rounded to fp32 first, then the outer one; p1 wins iff c_p1 > c_p0 (a tie takes p0); traceback from state 0.
+    Returns info (uint32 [n, W_i], MSB first, the last word's unused bits 0) and path (float32 [n], the final metric
+    of state 0)."""
+    lam = np.asarray(soft)
+    if lam.dtype != np.float32 or lam.ndim != 2 or lam.shape[1] % 96 or not 1 <= lam.shape[1] // 96 <= MAX_DATA_SYMBOLS:
+        raise ValueError(f"soft float32 [n, 96 D] with 1 <= D <= {MAX_DATA_SYMBOLS} expected, got {lam.dtype} {lam.shape}")
+    n, steps = len(lam), lam.shape[1] // 2
+    p0, a0, b0 = _trellis()
+    p1 = p0 | 1
+    m = np.full((n, CODE_STATES), -np.inf, np.float32)
+    m[:, 0] = 0
+    dec = np.zeros((steps, n, CODE_STATES), bool)
+    with np.errstate(invalid="ignore"):
+        for t in range(steps):
+            l0, l1 = lam[:, 2 * t, None], lam[:, 2 * t + 1, None]
+            sa, sb = np.where(a0, -l0, l0), np.where(b0, -l1, l1)
+            c0 = m[:, p0] + (sa + sb)
+            c1 = m[:, p1] + ((-sa) + (-sb))
+            dec[t] = c1 > c0
+            m = np.where(dec[t], c1, c0)
+    assert m.dtype == np.float32
+    s = np.zeros(n, np.int64)
+    u = np.zeros((n, steps), np.uint8)
+    rows = np.arange(n)
+    for t in range(steps - 1, -1, -1):
+        u[:, t] = s >> 5
+        s = ((2 * s) & 63) | dec[t, rows, s]
+    return dict(info=_pack_bits(u[:, :steps - CODE_TAIL]), path=m[:, 0].copy())
+
+
+def rrc_taps() -> np.ndarray:
+    """rcosdesign(0.5, 10, 2, 'sqrt') rounded to fp32 and made symmetric: the receivers' 21 matched-filter taps
+    (rrc_design, csrc/ofdm_capi.hip), float64 [21]"""
+    beta, sps = 0.5, 2.0
+    h = np.zeros(21)
+    for i in range(21):
+        t = (i - 10) / sps
+        q = 4 * beta * t
+        if t == 0.0:
+            h[i] = -1.0 / (np.pi * sps) * (np.pi * (beta - 1) - 4 * beta)
+        elif abs(abs(q) - 1.0) < 1e-12:
+            h[i] = 1.0 / (2 * np.pi * sps) * (np.pi * (beta + 1) * np.sin(np.pi * (beta + 1) / (4 * beta))
+                                               - 4 * beta * np.sin(np.pi * (beta - 1) / (4 * beta))
+                                               + np.pi * (beta - 1) * np.cos(np.pi * (beta - 1) / (4 * beta)))
+        else:
+            h[i] = -4 * beta / sps * (np.cos((1 + beta) * np.pi * t) + np.sin((1 - beta) * np.pi * t) / q) / (np.pi * (q * q - 1))
+    out = (h / np.sqrt((h * h).sum())).astype(np.float32)
+    out[11:] = out[:10][::-1]
+    return out.astype(np.float64)
+
+
+def _channel(r) -> np.ndarray:
+    """H = L S / 2, S = fft64(LTF1 + LTF2), of rotated frames r [..., >= 320]"""
+    return LTF_SIGNS * fft64(r[..., 192:256] + r[..., 256:320]) / 2
+
+
+def channel_gain(branches, positions, cfo_hz, taps=None) -> np.ndarray:
+    """The rule of ofdm_stream_csi (include/ofdm_mi355x_code.h) in double precision: float64 [n_packets, 48],
+    csi[i][m] = sum_b |H_b[bin(m)]|^2 over the 48 data bins in d_eq's order.  branches: B recordings [B, n] (or one,
+    [n]); positions: the records' packet_pos; cfo_hz: per packet, (double) cfo_coarse_hz + (double) cfo_fine_hz of the
+    record -- read, not re-estimated.  Per packet and branch: the matched filter at the frame instants 192 .. 319
+    (frame sample ii = sum_tt x[p + 2 ii - tt] taps[tt], samples outside [0, n) read as zero), the rotation by
+    exp(-j 2 pi f Ts ii), and H_b = L S_b / 2 with S_b = fft64(LTF1 + LTF2) as combine_branches forms them."""
+    xs = np.asarray(branches)
+    x = _branches([xs] if xs.ndim == 1 else xs)
+    n = x.shape[1]
+    h = rrc_taps() if taps is None else np.asarray(taps, np.float64)
+    pos = np.asarray(positions, np.int64).reshape(-1)
+    f = np.broadcast_to(np.asarray(cfo_hz, np.float64).reshape(-1), pos.shape)
+    out = np.zeros((len(pos), 48), np.float64)
+    ii = np.arange(192, 320)
+    pad = np.zeros((x.shape[0], 640 + 20), np.complex128)
+    for i, p in enumerate(pos):
+        p = int(p)
+        # stream samples p - 20 .. p + 639 at pad index s - (p - 20), zero outside the recording
+        pad[:] = 0
+        lo, hi = max(p - 20, 0), min(p + 640, n)
+        if lo < hi:
+            pad[:, lo - (p - 20):hi - (p - 20)] = x[:, lo:hi]
+        fr = np.zeros((x.shape[0], 320), np.complex128)
+        for tt in range(21):
+            fr[:, 192:] += pad[:, 20 + 2 * ii - tt] * h[tt]
+        H = _channel(_rotate(fr, float(f[i])))
+        out[i] = (np.abs(H[:, list(DATA_BINS)]) ** 2).sum(axis=0)
+    return out
 
 
 def transmit_main(argv=None) -> int:

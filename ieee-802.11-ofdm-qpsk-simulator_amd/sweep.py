@@ -176,7 +176,7 @@ def captures_main(argv=None):
 def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: float = 0.0, taps=None,
                noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=None, fading=None,
                detector: str = "reference", threshold: float = 0.75, timing: str = "none",
-               tracking: str = "none", branches: int = 1) -> dict:
+               tracking: str = "none", branches: int = 1, code: str | None = None) -> dict:
     """Packet-error and bit-error counts against SNR for packets that each carry their own bits, the recording never
     leaving the device: the packets (words: uint32 [n, 3 n_data], each behind `gap` idle samples, and a closing gap)
     are transmitted once; per SNR point q the clean recording is impaired into a second buffer with the noise stream
@@ -205,6 +205,14 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     (seed, trial B + b, q); the B recordings are received together (Engine.receive_diversity_device).  power is then the
     mean of the branches' realised powers, and every branch gets the noise power it sets.  B > 1 needs
     detector="conjugate"; with B = 1 every call and every total is what it was without the argument.
+    code: None, or "conv" (include/ofdm_mi355x_code.h): `words` are then information words
+    [n, abi.code_info_words(n_data)], encoded once (Engine.encode_packets) into the payload words that are transmitted;
+    per SNR point the receive call also returns d_eq, Engine.stream_csi forms the records' gains and Engine.decode_coded
+    the information words, which are gathered by the scores' rx_index and compared with the sent ones on the device.
+    The result then also holds info_totals (int64 [n_snr, 3]: information bits compared, information bit errors,
+    matched packets with at least one of them); totals are those of the coded payload bits before the decoder.  The SNR
+    axis stays per sample: at equal SNR a coded packet carries (48 D - 6) / 96 D of the bits.  With None every call and
+    every total is what it was without the argument.
 
     Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
     import torch  # noqa: PLC0415
@@ -229,9 +237,22 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
         raise ValueError(f"gap must not be negative, got {gap}")
     if gap < window[1]:
         raise ValueError(f"gap {gap} is shorter than the scoring window {tuple(window)}: a record could serve two packets")
+    if code not in (None, "conv"):
+        raise ValueError(f"code must be None or 'conv', got {code!r}")
     set_message(engine, " " * (12 * n_data))
     dev = torch.device("cuda", engine.device)
     w = words if torch.is_tensor(words) else torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(dev)
+    if code:
+        # the sent information words without the last word's unused bits (the decoder writes them as 0), then the payload
+        wi, kinfo = abi.code_info_words(n_data), abi.code_info_bits(n_data)
+        if w.dim() != 2 or w.shape[1] != wi:
+            raise ValueError(f"code='conv' takes information words [n, {wi}] for {n_data} data symbols, got {tuple(w.shape)}")
+        info = w.clone()
+        mask = (0xffffffff << (32 * wi - kinfo)) & 0xffffffff
+        info[:, -1] &= mask - (1 << 32) if mask >> 31 else mask
+        w = engine.encode_packets(info, n_data)
+        popcount = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int64, device=dev)
+        info_totals = torch.zeros((len(snr), 3), dtype=torch.int64, device=dev)
     nb = branches
     if pdp is None:
         stride = plen + gap
@@ -254,15 +275,33 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
         for b in range(nb):
             engine.impair_stream(clean[b], power, float(s), cfo_hz, taps=taps, noise=noise, seed=seed, trial=trial * nb + b,
                                  snr_index=q, out=rec[b])
+        if not code:
+            if nb == 1:
+                rx = engine.receive_stream_device(rec[0], detector=detector, threshold=threshold, timing=timing, tracking=tracking)
+            else:
+                rx = engine.receive_diversity_device(rec, detector=detector, threshold=threshold, timing=timing, tracking=tracking)
+            engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])
+            continue
         if nb == 1:
-            rx = engine.receive_stream_device(rec[0], detector=detector, threshold=threshold, timing=timing, tracking=tracking)
+            rx = engine.receive_stream_device(rec[0], detector=detector, threshold=threshold, timing=timing, tracking=tracking,
+                                              want_eq=True)
         else:
-            rx = engine.receive_diversity_device(rec, detector=detector, threshold=threshold, timing=timing, tracking=tracking)
-        engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])
-    return dict(snr_db=snr, totals=totals.cpu().numpy(), power=power, packets=n, samples=n_out)
+            rx = engine.receive_diversity_device(rec, detector=detector, threshold=threshold, timing=timing, tracking=tracking,
+                                                 want_eq=True)
+        got = engine.decode_coded(rx, csi=engine.stream_csi(rec if nb > 1 else rec[0], rx))["d_info"]
+        idx = engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])["scores"][:, 0].long()
+        matched = idx >= 0
+        diff = (got[idx.clamp(min=0)] ^ info).contiguous().view(torch.uint8)
+        err = torch.where(matched, popcount[diff.long()].sum(dim=1), torch.zeros_like(idx))
+        info_totals[q] += torch.stack([matched.sum() * kinfo, err.sum(), (err > 0).sum()])
+    out = dict(snr_db=snr, totals=totals.cpu().numpy(), power=power, packets=n, samples=n_out)
+    if code:
+        out.update(info_totals=info_totals.cpu().numpy())
+    return out
 
 
 LINK_COLUMNS = ("snr_db", "transmitted", "matched", "missed", "false_alarms", "packet_err", "bit_err", "bits")
+LINK_CODE_COLUMNS = ("info_bits", "info_bit_err", "info_packet_err")     # --code conv: three trailing columns
 
 
 def parse_snr_grid(text: str) -> np.ndarray:
@@ -282,7 +321,7 @@ def link_main(argv=None) -> int:
     import csv  # noqa: PLC0415
     from .channel import NOISE_KINDS, parse_pdp, parse_taps  # noqa: PLC0415
     from .fileio import write_float_array_to_file  # noqa: PLC0415
-    from .stream import pack_messages  # noqa: PLC0415
+    from .stream import pack_coded_messages, pack_messages  # noqa: PLC0415
     ap = argparse.ArgumentParser(prog="ofdm_pkg.py link", description=link_main.__doc__)
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--packets", type=int, help="packets of random payload bits (drawn from --seed)")
@@ -310,6 +349,9 @@ def link_main(argv=None) -> int:
     ap.add_argument("--branches", type=int, default=1,
                     help=f"receive antennas, 1 to {abi.DIVERSITY_MAX_BRANCHES}: independently faded and independently noisy "
                          "recordings of the same packets, combined in the receiver (more than 1 needs --detector conjugate)")
+    ap.add_argument("--code", choices=["conv"], default=None,
+                    help="conv: the packets carry 48 D - 6 information bits through 802.11a's K = 7 rate-1/2 code; the receiver's "
+                         "equalised subcarriers go through a soft Viterbi decoder weighted with the channel's gains")
     ap.add_argument("--out", default="data")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:
@@ -326,35 +368,43 @@ def link_main(argv=None) -> int:
         texts = [ln for ln in Path(a.messages).read_text(encoding="latin-1").splitlines() if ln]
         if not texts:
             raise SystemExit(f"{a.messages}: no lines")
-        words, d = pack_messages(texts, a.n_data)
+        words, d = (pack_coded_messages if a.code else pack_messages)(texts, a.n_data)
     else:
         if a.packets < 0:
             raise SystemExit("--packets must not be negative")
         d = 2 if a.n_data is None else a.n_data
         if not 1 <= d <= abi.LONG_MAX_DATA_SYMBOLS:
             raise SystemExit(f"--n-data must be in [1, {abi.LONG_MAX_DATA_SYMBOLS}]")
-        words = np.random.default_rng(a.seed).integers(0, 1 << 32, (a.packets, 3 * d), dtype=np.uint64).astype(np.uint32)
+        nw = abi.code_info_words(d) if a.code else 3 * d
+        words = np.random.default_rng(a.seed).integers(0, 1 << 32, (a.packets, nw), dtype=np.uint64).astype(np.uint32)
     out = Path(a.out)
     out.mkdir(parents=True, exist_ok=True)
     t0 = time.perf_counter()
     with Engine(0) as eng:
         res = link_sweep(eng, words, d, a.gap, snr, cfo_hz=a.cfo_hz, taps=None if a.taps is None else parse_taps(a.taps),
                          noise=a.noise, seed=a.seed, fading=fading, detector=a.detector, threshold=a.threshold,
-                         timing=a.timing, tracking=a.tracking, branches=a.branches)
+                         timing=a.timing, tracking=a.tracking, branches=a.branches, code=a.code)
     wall = time.perf_counter() - t0
     t = res["totals"]
+    it = res.get("info_totals")
     ber = t[:, abi.S_BIT_ERR] / np.maximum(t[:, abi.S_BITS], 1)
     write_float_array_to_file(snr, out / "Output_SNR.txt")
-    write_float_array_to_file(ber, out / "Output_BER.txt")
+    # with a code the file holds the information BER
+    write_float_array_to_file(ber if it is None else it[:, 1] / np.maximum(it[:, 0], 1), out / "Output_BER.txt")
     with open(out / "link.csv", "w", newline="") as f:
         wr = csv.writer(f)
-        wr.writerow(LINK_COLUMNS)
-        for s, r in zip(snr, t):
+        wr.writerow(LINK_COLUMNS if it is None else LINK_COLUMNS + LINK_CODE_COLUMNS)
+        for q, (s, r) in enumerate(zip(snr, t)):
             tx, matched, received = int(r[abi.S_TRANSMITTED]), int(r[abi.S_MATCHED]), int(r[abi.S_RECEIVED])
-            wr.writerow([f"{s:g}", tx, matched, tx - matched, received - matched, int(r[abi.S_PACKET_ERR]),
-                         int(r[abi.S_BIT_ERR]), int(r[abi.S_BITS])])
-            print(f"SNR = {s:5.1f} dB   matched {matched}/{tx}   false alarms {received - matched}   "
-                  f"BER = {r[abi.S_BIT_ERR] / max(int(r[abi.S_BITS]), 1):.3e}", file=sys.stderr)
+            row = [f"{s:g}", tx, matched, tx - matched, received - matched, int(r[abi.S_PACKET_ERR]),
+                   int(r[abi.S_BIT_ERR]), int(r[abi.S_BITS])]
+            line = (f"SNR = {s:5.1f} dB   matched {matched}/{tx}   false alarms {received - matched}   "
+                    f"BER = {r[abi.S_BIT_ERR] / max(int(r[abi.S_BITS]), 1):.3e}")
+            if it is not None:
+                row += [int(v) for v in it[q]]
+                line += f"   information BER = {it[q, 1] / max(int(it[q, 0]), 1):.3e}"
+            wr.writerow(row)
+            print(line, file=sys.stderr)
     print(f"{res['packets']} packets of {d} data symbols, {res['samples']} samples, {len(snr)} SNR points in {wall:.2f} s "
           f"-> {out / 'link.csv'}", file=sys.stderr)
     return 0

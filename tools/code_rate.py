@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Times of the coded link's three kernels (include/ofdm_mi355x_code.h, csrc/ofdm_code.hip) on one GPU: the encoder, the
+gains kernel and the Viterbi decoder, for 2^16 packets of D = 2 and D = 15 data symbols on B = 1 and 2 branches.
+
+Per case: random information words are encoded and transmitted behind 500-sample idle gaps, every branch gets 20 dB of
+complex noise of its own, and `--launches` rounds of receive (conjugate detector, OFDM_TIMING_LTF, with d_eq; pilot
+tracking for D = 15) -> ofdm_stream_csi -> ofdm_code_decode run after a warm-up round.  Times are the library's own
+events (ofdm_timing_query), reset before and read after the rounds: per launch for ids 18 (encode), 19 (gains), 20
+(decode) and for the stream decode kernel of the same receive call (6, 14 or 17); the gains and the Viterbi decoder
+are also given as ratios to that kernel.  Writes one JSON record under profiles/r20/code/.
+
+    python tools/code_rate.py [--packets N] [--launches K] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+SNR_DB, GAP = 20.0, 500
+CASES = ((2, 1), (2, 2), (15, 1), (15, 2))      # (D, B)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--packets", type=int, default=1 << 16)
+    ap.add_argument("--launches", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args(argv)
+    out = Path(a.out) if a.out else ROOT / "profiles" / "r20" / "code" / f"code_rate_{a.packets}.json"
+    import torch  # noqa: PLC0415
+    import ofdm_pkg  # noqa: PLC0415
+    pkg = ofdm_pkg.load()
+    from ofdm_amd import abi, build_lib  # noqa: PLC0415
+
+    n = a.packets
+    record = dict(tool="tools/code_rate.py", device=torch.cuda.get_device_name(0), packets=n, launches=a.launches,
+                  snr_db=SNR_DB, gap=GAP, cases=[])
+    rng = np.random.default_rng(0xC0DE)
+    with pkg.Engine(0) as eng:
+        for d, nb in CASES:
+            eng.set_long_message(" " * (12 * d))
+            info = rng.integers(0, 1 << 32, (n, abi.code_info_words(d)), dtype=np.uint64).astype(np.uint32)
+            tinfo = torch.from_numpy(info.view(np.int32)).cuda()
+            stride = abi.packet_len(d) + GAP
+            eng.timing(True)
+            eng.timing_reset()
+            for _ in range(a.launches + 1):
+                words = eng.encode_packets(tinfo, d)
+            enc_ms, enc_n = eng.timing_query(abi.K_CODE_ENCODE)
+            clean = eng.transmit_packets(words, d, pos0=GAP, stride=stride, n_out=n * stride + GAP)
+            power = float((clean.real.double() ** 2 + clean.imag.double() ** 2).sum()) / (n * abi.packet_len(d))
+            rec = [eng.impair_stream(clean, power, SNR_DB, noise="complex", trial=b) for b in range(nb)]
+            del clean
+            tracking = "pilots" if d == 15 else "none"
+            dec_id = abi.K_STREAM_DECODE_DIV if nb > 1 else abi.K_STREAM_DECODE_TRACK if d == 15 else abi.K_STREAM_DECODE
+
+            def round_():
+                if nb == 1:
+                    rx = eng.receive_stream_device(rec[0], detector="conjugate", timing="ltf", tracking=tracking, want_eq=True)
+                else:
+                    rx = eng.receive_diversity_device(rec, detector="conjugate", timing="ltf", tracking=tracking, want_eq=True)
+                csi = eng.stream_csi(rec if nb > 1 else rec[0], rx)
+                return rx, eng.decode_coded(rx, csi=csi)
+            round_()                                                  # warm-up
+            eng.timing_reset()
+            for _ in range(a.launches):
+                rx, dec = round_()
+            eng.synchronize()
+            per = {}
+            for name, k in (("stream_decode", dec_id), ("stream_csi", abi.K_STREAM_CSI), ("code_decode", abi.K_CODE_DECODE)):
+                ms, cnt = eng.timing_query(k)
+                assert cnt == a.launches, (name, cnt)
+                per[name] = ms / cnt
+            eng.timing(False)
+            count = int(rx["d_count"].cpu()[1])
+            case = dict(n_data=d, branches=nb, samples=n * stride + GAP, received=count,
+                        encode_ms=enc_ms / enc_n, stream_decode_kernel=dec_id, stream_decode_ms=per["stream_decode"],
+                        stream_csi_ms=per["stream_csi"], code_decode_ms=per["code_decode"],
+                        csi_over_stream_decode=per["stream_csi"] / per["stream_decode"],
+                        code_decode_over_stream_decode=per["code_decode"] / per["stream_decode"])
+            record["cases"].append(case)
+            print(json.dumps(case), file=sys.stderr)
+            del rec, rx, dec
+            torch.cuda.empty_cache()
+    report = json.loads(build_lib.RESOURCE_REPORT.read_text())
+    record["resources"] = {r["name"]: {k: r[k] for k in ("VGPRs", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")}
+                           for r in report if r.get("source") == "ofdm_code.hip"}
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(record, indent=1))
+    print(f"-> {out}", file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
