@@ -219,6 +219,44 @@ def code_decode_lds_bytes(n_data: int) -> int:
     return CODE_DECODE_WAVES * (96 * int(n_data) * 4 + 48 * int(n_data) * 8)
 
 
+# the extension header include/ofdm_mi355x_punct.h (802.11a's punctured rates 2/3 and 3/4 of the coded link: an encoder
+# and a Viterbi decoder that take a rate); the export lists above and ABI_VERSION do not change with it
+PUNCT_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_punct.h"
+_PUNCT_SIGS = {
+    "ofdm_punct_encode": (C.c_int, [_V, C.c_int32, C.c_int32, _V, C.c_int64, _V]),
+    "ofdm_punct_decode": (C.c_int, [_V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int64, _V, _V]),
+}
+PUNCT_FUNCTIONS = tuple(_PUNCT_SIGS)
+RATE = {"1/2": 0, "2/3": 1, "3/4": 2}            # OFDM_PUNCT_RATE_*
+PUNCT_STEPS = (48, 64, 72)                       # OFDM_PUNCT_STEPS: trellis steps per data symbol, by rate code
+
+
+def rate_code(rate: str) -> int:
+    """OFDM_PUNCT_RATE_* of "1/2", "2/3" or "3/4"; ValueError for anything else"""
+    if not isinstance(rate, str) or rate not in RATE:
+        raise ValueError(f"rate must be one of {tuple(RATE)}, got {rate!r}")
+    return RATE[rate]
+
+
+def punct_info_bits(n_data: int, rate: str) -> int:
+    """OFDM_PUNCT_INFO_BITS: S D - 6"""
+    return PUNCT_STEPS[rate_code(rate)] * int(n_data) - CODE_TAIL_BITS
+
+
+def punct_info_words(n_data: int, rate: str) -> int:
+    """OFDM_PUNCT_INFO_WORDS: ceil((S D - 6) / 32)"""
+    return (punct_info_bits(n_data, rate) + 31) // 32
+
+
+PUNCT_DECODE_WAVES = 2                           # PDEC_WAVES (csrc/ofdm_punct.hip): rows per block and sweep
+
+
+def punct_decode_lds_bytes(n_data: int, rate: str) -> int:
+    """The punctured decode kernel's dynamic LDS per block: per wave S D 64-bit words (the decisions) and the 96 D sent
+    soft values as floats, 14,400 bytes at rate 3/4 and D = 15; it has no static LDS."""
+    return PUNCT_DECODE_WAVES * (PUNCT_STEPS[rate_code(rate)] * int(n_data) * 8 + 96 * int(n_data) * 4)
+
+
 class OfdmError(RuntimeError):
     pass
 
@@ -436,7 +474,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib = C.CDLL(str(p))
     for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS,
                               **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS, **_TIMING_SIGS, **_TRACK_SIGS,
-                              **_DIVERSITY_SIGS, **_CODE_SIGS}.items():
+                              **_DIVERSITY_SIGS, **_CODE_SIGS, **_PUNCT_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

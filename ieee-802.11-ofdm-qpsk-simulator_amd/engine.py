@@ -769,17 +769,20 @@ class Engine:
         return res
 
     # ---- the coded link (include/ofdm_mi355x_code.h) ------------------------------------
-    def encode_packets(self, info, n_data: int):
+    def encode_packets(self, info, n_data: int, rate: str = "1/2"):
         """Information words -> payload words on the device (ofdm_code_encode; stream.conv_encode is the rule): the
         K = 7 rate-1/2 code, the per-symbol interleaver and the precoding for the reference's QPSK map.  info: uint32
         or int32 [n, W_i] (abi.code_info_words(n_data)), a numpy array (uploaded) or a contiguous tensor on this engine's
-        device.  Returns an int32 device tensor [n, 3 n_data], what transmit_packets and transmit_faded take."""
+        device.  Returns an int32 device tensor [n, 3 n_data], what transmit_packets and transmit_faded take.
+        rate: "1/2", or "2/3" or "3/4" (include/ofdm_mi355x_punct.h: ofdm_punct_encode; stream.conv_encode_rate is the
+        rule); W_i is then abi.punct_info_words(n_data, rate)."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
+        rcode = abi.rate_code(rate)
         nd = int(n_data)
         if nd != n_data or not 1 <= nd <= abi.LONG_MAX_DATA_SYMBOLS:
             raise ValueError(f"n_data must be in [1, {abi.LONG_MAX_DATA_SYMBOLS}], got {n_data!r}")
-        wi = abi.code_info_words(nd)
+        wi = abi.punct_info_words(nd, rate)
         if isinstance(info, np.ndarray):
             if info.dtype not in (np.uint32, np.int32) or info.ndim != 2:
                 raise ValueError(f"info must be uint32 [n, {wi}], got {info.dtype} {info.shape}")
@@ -790,8 +793,10 @@ class Engine:
             raise ValueError(f"info must be contiguous on {dev}")
         n = int(info.shape[0])
         words = torch.empty((n, 3 * nd), dtype=torch.int32, device=dev)
-        if n:
+        if n and rcode == 0:
             check(self.lib, self.lib.ofdm_code_encode(self.ctx, nd, _ptr(info), n, _ptr(words)), "code_encode")
+        elif n:
+            check(self.lib, self.lib.ofdm_punct_encode(self.ctx, rcode, nd, _ptr(info), n, _ptr(words)), "punct_encode")
         return words
 
     def stream_csi(self, branches_or_samples, rx: dict):
@@ -815,15 +820,17 @@ class Engine:
               "stream_csi")
         return csi
 
-    def decode_coded(self, rx, csi=None, want_path: bool = False, n_data: int | None = None) -> dict:
+    def decode_coded(self, rx, csi=None, want_path: bool = False, n_data: int | None = None, rate: str = "1/2") -> dict:
         """The soft Viterbi decoder over equalised subcarriers (ofdm_code_decode; stream.conv_soft and
         stream.viterbi_decode are the rule, bit for bit).  rx: a receive call's result with d_eq and d_count
         (want_eq=True), or a complex64 device tensor [n, 48 D] to decode whole.  csi: stream_csi's tensor, or None for
         unweighted soft values.  Returns d_info (int32 [rows, W_i], MSB first; with rx a result, the first d_count[1]
         rows are written) and d_path (float32 [rows], the path metric; None without want_path).  Nothing waits for the
-        device."""
+        device.  rate: "1/2", or "2/3" or "3/4" (include/ofdm_mi355x_punct.h: ofdm_punct_decode; stream.conv_soft_rate and
+        stream.viterbi_decode_rate are the rule, bit for bit); W_i is then abi.punct_info_words(D, rate)."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
+        rcode = abi.rate_code(rate)
         if isinstance(rx, dict):
             eq, cnt = rx.get("d_eq"), rx["d_count"]
             if eq is None:
@@ -843,12 +850,15 @@ class Engine:
             if not (torch.is_tensor(csi) and csi.dtype == torch.float32 and csi.device == dev and csi.is_contiguous()
                     and tuple(csi.shape) == (n, 48)):
                 raise ValueError(f"csi must be a contiguous float32 device tensor [{n}, 48]")
-        info = torch.empty((n, abi.code_info_words(nd)), dtype=torch.int32, device=dev)
+        info = torch.empty((n, abi.punct_info_words(nd, rate)), dtype=torch.int32, device=dev)
         path = torch.empty(n, dtype=torch.float32, device=dev) if want_path else None
         opt = lambda x: None if x is None else _ptr(x)
-        if n:
+        if n and rcode == 0:
             check(self.lib, self.lib.ofdm_code_decode(self.ctx, nd, _ptr(eq), opt(csi), opt(cnt), n, _ptr(info), opt(path)),
                   "code_decode")
+        elif n:
+            check(self.lib, self.lib.ofdm_punct_decode(self.ctx, rcode, nd, _ptr(eq), opt(csi), opt(cnt), n, _ptr(info),
+                                                       opt(path)), "punct_decode")
         return dict(d_info=info, d_path=path, frames=nd)
 
     @staticmethod

@@ -455,24 +455,29 @@ def INFO_WORDS(n_data: int) -> int:
     return (INFO_BITS(n_data) + 31) // 32
 
 
-def pack_coded_messages(texts, n_data: int | None = None):
+def pack_coded_messages(texts, n_data: int | None = None, rate: str = "1/2"):
     """Information words of one coded packet per text: (uint32 [n, W_i], D).  A text (str, latin-1, or bytes) fills the
     first 8 len information bits, MSB first, and is padded with ' ' to the K_info // 8 whole characters a packet holds;
-    the few bits past them are 0.  D is n_data, or the smallest with 48 D - 6 >= 8 len for every text (at least 1).
+    the few bits past them are 0.  D is n_data, or the smallest with S D - 6 >= 8 len for every text (at least 1); S is
+    48, or RATE_STEPS[rate] at a punctured rate (include/ofdm_mi355x_punct.h).
     ValueError for a text that needs more than 15 symbols or more than n_data."""
+    if rate not in RATE_STEPS:
+        raise ValueError(f"rate must be one of {tuple(RATE_STEPS)}, got {rate!r}")
+    s = RATE_STEPS[rate]
+    kinfo = lambda d: s * d - CODE_TAIL
     rows = [t.encode("latin-1") if isinstance(t, str) else bytes(t) for t in texts]
-    need = [max((8 * len(b) + CODE_TAIL + 47) // 48, 1) for b in rows]
+    need = [max((8 * len(b) + CODE_TAIL + s - 1) // s, 1) for b in rows]
     for b, k in zip(rows, need):
         if k > MAX_DATA_SYMBOLS:
             raise ValueError(f"a text of {len(b)} characters needs {k} data symbols, a coded packet carries at most "
-                             f"{MAX_DATA_SYMBOLS} ({INFO_BITS(MAX_DATA_SYMBOLS) // 8} characters)")
+                             f"{MAX_DATA_SYMBOLS} ({kinfo(MAX_DATA_SYMBOLS) // 8} characters)")
     d = max(need, default=1) if n_data is None else int(n_data)
     if not 1 <= d <= MAX_DATA_SYMBOLS:
         raise ValueError(f"n_data must be in [1, {MAX_DATA_SYMBOLS}], got {n_data!r}")
     if need and max(need) > d:
         raise ValueError(f"a text needs {max(need)} data symbols, n_data is {d}")
-    buf = np.zeros((len(rows), 4 * INFO_WORDS(d)), np.uint8)
-    buf[:, :INFO_BITS(d) // 8] = 0x20
+    buf = np.zeros((len(rows), 4 * ((kinfo(d) + 31) // 32)), np.uint8)
+    buf[:, :kinfo(d) // 8] = 0x20
     for k, b in enumerate(rows):
         buf[k, :len(b)] = np.frombuffer(b, np.uint8)
     return buf.view(">u4").astype(np.uint32), d
@@ -567,17 +572,9 @@ def _trellis():
     return (2 * s) & 63, a0.astype(bool), b0.astype(bool)
 
 
-def viterbi_decode(soft) -> dict:
-    """The decoder of include/ofdm_mi355x_code.h in fp32, its executable specification, vectorised over packets.
-    soft: float32 [n, 96 D] in trellis order (conv_soft).  A Viterbi decoder over the 64 states with a correlation
-    metric that is maximised: M = 0 for state 0 and -inf for the others; per step and new state the two candidates
-    c_p = M[p] + ((+-lam[2 t]) + (+-lam[2 t + 1])), the sign "-" where the branch's coded bit is 1, the inner sum
-    rounded to fp32 first, then the outer one; p1 wins iff c_p1 > c_p0 (a tie takes p0); traceback from state 0.
-    Returns info (uint32 [n, W_i], MSB first, the last word's unused bits 0) and path (float32 [n], the final metric
-    of state 0)."""
-    lam = np.asarray(soft)
-    if lam.dtype != np.float32 or lam.ndim != 2 or lam.shape[1] % 96 or not 1 <= lam.shape[1] // 96 <= MAX_DATA_SYMBOLS:
-        raise ValueError(f"soft float32 [n, 96 D] with 1 <= D <= {MAX_DATA_SYMBOLS} expected, got {lam.dtype} {lam.shape}")
+def _viterbi(lam) -> dict:
+    """The recursion and traceback of viterbi_decode over float32 [n, 2 T] values, T steps of which the last six are
+    the tail"""
     n, steps = len(lam), lam.shape[1] // 2
     p0, a0, b0 = _trellis()
     p1 = p0 | 1
@@ -600,6 +597,98 @@ def viterbi_decode(soft) -> dict:
         u[:, t] = s >> 5
         s = ((2 * s) & 63) | dec[t, rows, s]
     return dict(info=_pack_bits(u[:, :steps - CODE_TAIL]), path=m[:, 0].copy())
+
+
+def viterbi_decode(soft) -> dict:
+    """The decoder of include/ofdm_mi355x_code.h in fp32, its executable specification, vectorised over packets.
+    soft: float32 [n, 96 D] in trellis order (conv_soft).  A Viterbi decoder over the 64 states with a correlation
+    metric that is maximised: M = 0 for state 0 and -inf for the others; per step and new state the two candidates
+    c_p = M[p] + ((+-lam[2 t]) + (+-lam[2 t + 1])), the sign "-" where the branch's coded bit is 1, the inner sum
+    rounded to fp32 first, then the outer one; p1 wins iff c_p1 > c_p0 (a tie takes p0); traceback from state 0.
+    Returns info (uint32 [n, W_i], MSB first, the last word's unused bits 0) and path (float32 [n], the final metric
+    of state 0)."""
+    lam = np.asarray(soft)
+    if lam.dtype != np.float32 or lam.ndim != 2 or lam.shape[1] % 96 or not 1 <= lam.shape[1] // 96 <= MAX_DATA_SYMBOLS:
+        raise ValueError(f"soft float32 [n, 96 D] with 1 <= D <= {MAX_DATA_SYMBOLS} expected, got {lam.dtype} {lam.shape}")
+    return _viterbi(lam)
+
+
+# ---- the punctured rates (include/ofdm_mi355x_punct.h): 802.11a's 2/3 and 3/4 of the same code ----
+RATES = ("1/2", "2/3", "3/4")                          # OFDM_PUNCT_RATE_*: the C codes 0, 1, 2
+RATE_STEPS = {"1/2": 48, "2/3": 64, "3/4": 72}         # S: trellis steps per data symbol of 96 sent bits
+# the period of each pattern as (step, 0: A, 1: B) in sent order
+_RATE_PERIOD = {"1/2": (1, ((0, 0), (0, 1))),
+                "2/3": (2, ((0, 0), (0, 1), (1, 0))),
+                "3/4": (3, ((0, 0), (0, 1), (1, 0), (2, 1)))}
+
+
+def _rate(rate) -> str:
+    if not isinstance(rate, str) or rate not in RATES:
+        raise ValueError(f"rate must be one of {RATES}, got {rate!r}")
+    return rate
+
+
+def puncture_index(rate: str) -> np.ndarray:
+    """The 96 kept places of a data symbol's 2 S coded bits (place 2 tau + 0 is A_tau, 2 tau + 1 is B_tau), in sent
+    order.  802.11a's patterns, restarting at every symbol: rate 2/3 sends A_tau always and B_tau for even tau; rate
+    3/4 sends A_tau for tau mod 3 != 2 and B_tau for tau mod 3 != 1; rate 1/2 sends everything."""
+    period, kept = _RATE_PERIOD[_rate(rate)]
+    s = RATE_STEPS[rate]
+    idx = np.array([2 * (period * p + tau) + ab for p in range(s // period) for tau, ab in kept], np.int64)
+    assert len(idx) == 96
+    return idx
+
+
+def rate_info_bits(n_data: int, rate: str = "1/2") -> int:
+    """K_info = S D - 6 information bits of a packet of D data symbols at a rate"""
+    return INFO_BITS(n_data) + (RATE_STEPS[_rate(rate)] - 48) * int(n_data)
+
+
+def rate_info_words(n_data: int, rate: str = "1/2") -> int:
+    """W_i = ceil(K_info / 32) words of uint32 per packet, MSB first"""
+    return (rate_info_bits(n_data, rate) + 31) // 32
+
+
+def conv_encode_rate(info_words, n_data: int, rate: str = "1/2") -> np.ndarray:
+    """The encoder of include/ofdm_mi355x_punct.h, its executable specification: information words uint32
+    [n, rate_info_words(n_data, rate)] -> payload words uint32 [n, 3 D].  K_info = S D - 6 information bits and six zero
+    tail bits through the mother code; of each data symbol's 2 S coded bits the 96 of puncture_index(rate) are sent,
+    through conv_encode's interleaver and precoding.  Rate "1/2" is conv_encode."""
+    kinfo, wi = rate_info_bits(n_data, rate), rate_info_words(n_data, rate)
+    w = np.ascontiguousarray(np.asarray(info_words).astype(np.uint32, copy=False))
+    if w.ndim != 2 or w.shape[1] != wi:
+        raise ValueError(f"information words [n, {wi}] expected for {n_data} data symbols at rate {rate}, got {w.shape}")
+    u = np.unpackbits(w.astype(">u4").view(np.uint8), axis=1)[:, :kinfo]
+    n = len(u)
+    u = np.concatenate([u, np.zeros((n, CODE_TAIL), np.uint8)], axis=1)
+    c = conv_code_bits(u).reshape(n, n_data, 2 * RATE_STEPS[rate])[:, :, puncture_index(rate)]
+    g = np.zeros_like(c)
+    g[:, :, interleave_index()] = c
+    g[:, :, 1::2] ^= g[:, :, 0::2]
+    return _pack_bits(g.reshape(n, 96 * n_data))
+
+
+def conv_soft_rate(eq, csi=None, rate: str = "1/2") -> np.ndarray:
+    """The soft values of include/ofdm_mi355x_punct.h: float32 [n, 2 S D], the two of step t at 2 t and 2 t + 1.  A sent
+    position's value is conv_soft's (eq, csi: as there); a stolen place holds +0.0."""
+    idx = puncture_index(rate)
+    sent = conv_soft(eq, csi)
+    n, d, s = len(sent), sent.shape[1] // 96, RATE_STEPS[rate]
+    out = np.zeros((n, d, 2 * s), np.float32)
+    out[:, :, idx] = sent.reshape(n, d, 96)
+    return out.reshape(n, 2 * s * d)
+
+
+def viterbi_decode_rate(soft, rate: str = "1/2") -> dict:
+    """The decoder of include/ofdm_mi355x_punct.h in fp32: viterbi_decode's rule, unchanged, over the S D steps of
+    conv_soft_rate's float32 [n, 2 S D]; an erased value takes part as the +0.0 it is.  Returns info (uint32
+    [n, rate_info_words(D, rate)]) and path (float32 [n])."""
+    s2 = 2 * RATE_STEPS[_rate(rate)]
+    lam = np.asarray(soft)
+    if lam.dtype != np.float32 or lam.ndim != 2 or lam.shape[1] % s2 or not 1 <= lam.shape[1] // s2 <= MAX_DATA_SYMBOLS:
+        raise ValueError(f"soft float32 [n, {s2} D] with 1 <= D <= {MAX_DATA_SYMBOLS} expected at rate {rate}, got "
+                         f"{lam.dtype} {lam.shape}")
+    return _viterbi(lam)
 
 
 def rrc_taps() -> np.ndarray:

@@ -176,7 +176,7 @@ def captures_main(argv=None):
 def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: float = 0.0, taps=None,
                noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=None, fading=None,
                detector: str = "reference", threshold: float = 0.75, timing: str = "none",
-               tracking: str = "none", branches: int = 1, code: str | None = None) -> dict:
+               tracking: str = "none", branches: int = 1, code: str | None = None, rate: str = "1/2") -> dict:
     """Packet-error and bit-error counts against SNR for packets that each carry their own bits, the recording never
     leaving the device: the packets (words: uint32 [n, 3 n_data], each behind `gap` idle samples, and a closing gap)
     are transmitted once; per SNR point q the clean recording is impaired into a second buffer with the noise stream
@@ -213,6 +213,10 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     matched packets with at least one of them); totals are those of the coded payload bits before the decoder.  The SNR
     axis stays per sample: at equal SNR a coded packet carries (48 D - 6) / 96 D of the bits.  With None every call and
     every total is what it was without the argument.
+    rate: "1/2", or with code="conv" one of 802.11a's punctured rates "2/3" and "3/4" (include/ofdm_mi355x_punct.h,
+    DESIGN.md K21): `words` are then [n, abi.punct_info_words(n_data, rate)], S D - 6 information bits per packet with
+    S = 64 or 72, and the encoder and decoder are the punctured ones; info_totals keep their meaning.  With "1/2" every
+    call is what it was without the argument.
 
     Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
     import torch  # noqa: PLC0415
@@ -239,18 +243,21 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
         raise ValueError(f"gap {gap} is shorter than the scoring window {tuple(window)}: a record could serve two packets")
     if code not in (None, "conv"):
         raise ValueError(f"code must be None or 'conv', got {code!r}")
+    if abi.rate_code(rate) and not code:
+        raise ValueError(f"rate {rate!r} needs code='conv'")
     set_message(engine, " " * (12 * n_data))
     dev = torch.device("cuda", engine.device)
     w = words if torch.is_tensor(words) else torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(dev)
     if code:
         # the sent information words without the last word's unused bits (the decoder writes them as 0), then the payload
-        wi, kinfo = abi.code_info_words(n_data), abi.code_info_bits(n_data)
+        wi, kinfo = abi.punct_info_words(n_data, rate), abi.punct_info_bits(n_data, rate)
         if w.dim() != 2 or w.shape[1] != wi:
-            raise ValueError(f"code='conv' takes information words [n, {wi}] for {n_data} data symbols, got {tuple(w.shape)}")
+            raise ValueError(f"code='conv' takes information words [n, {wi}] for {n_data} data symbols"
+                             f"{'' if rate == '1/2' else ' at rate ' + rate}, got {tuple(w.shape)}")
         info = w.clone()
         mask = (0xffffffff << (32 * wi - kinfo)) & 0xffffffff
         info[:, -1] &= mask - (1 << 32) if mask >> 31 else mask
-        w = engine.encode_packets(info, n_data)
+        w = engine.encode_packets(info, n_data, rate=rate)
         popcount = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int64, device=dev)
         info_totals = torch.zeros((len(snr), 3), dtype=torch.int64, device=dev)
     nb = branches
@@ -288,7 +295,7 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
         else:
             rx = engine.receive_diversity_device(rec, detector=detector, threshold=threshold, timing=timing, tracking=tracking,
                                                  want_eq=True)
-        got = engine.decode_coded(rx, csi=engine.stream_csi(rec if nb > 1 else rec[0], rx))["d_info"]
+        got = engine.decode_coded(rx, csi=engine.stream_csi(rec if nb > 1 else rec[0], rx), rate=rate)["d_info"]
         idx = engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])["scores"][:, 0].long()
         matched = idx >= 0
         diff = (got[idx.clamp(min=0)] ^ info).contiguous().view(torch.uint8)
@@ -352,10 +359,15 @@ def link_main(argv=None) -> int:
     ap.add_argument("--code", choices=["conv"], default=None,
                     help="conv: the packets carry 48 D - 6 information bits through 802.11a's K = 7 rate-1/2 code; the receiver's "
                          "equalised subcarriers go through a soft Viterbi decoder weighted with the channel's gains")
+    ap.add_argument("--rate", choices=tuple(abi.RATE), default="1/2",
+                    help="with --code conv: the code's rate; 2/3 and 3/4 are 802.11a's punctured rates, 64 D - 6 and 72 D - 6 "
+                         "information bits per packet")
     ap.add_argument("--out", default="data")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:
         raise SystemExit("--threshold must be inside (0, 1)")
+    if a.rate != "1/2" and not a.code:
+        raise SystemExit(f"--rate {a.rate} needs --code conv")
     if not 1 <= a.branches <= abi.DIVERSITY_MAX_BRANCHES:
         raise SystemExit(f"--branches must be in [1, {abi.DIVERSITY_MAX_BRANCHES}]")
     if a.branches > 1 and a.detector != "conjugate":
@@ -368,14 +380,14 @@ def link_main(argv=None) -> int:
         texts = [ln for ln in Path(a.messages).read_text(encoding="latin-1").splitlines() if ln]
         if not texts:
             raise SystemExit(f"{a.messages}: no lines")
-        words, d = (pack_coded_messages if a.code else pack_messages)(texts, a.n_data)
+        words, d = pack_coded_messages(texts, a.n_data, a.rate) if a.code else pack_messages(texts, a.n_data)
     else:
         if a.packets < 0:
             raise SystemExit("--packets must not be negative")
         d = 2 if a.n_data is None else a.n_data
         if not 1 <= d <= abi.LONG_MAX_DATA_SYMBOLS:
             raise SystemExit(f"--n-data must be in [1, {abi.LONG_MAX_DATA_SYMBOLS}]")
-        nw = abi.code_info_words(d) if a.code else 3 * d
+        nw = abi.punct_info_words(d, a.rate) if a.code else 3 * d
         words = np.random.default_rng(a.seed).integers(0, 1 << 32, (a.packets, nw), dtype=np.uint64).astype(np.uint32)
     out = Path(a.out)
     out.mkdir(parents=True, exist_ok=True)
@@ -383,7 +395,7 @@ def link_main(argv=None) -> int:
     with Engine(0) as eng:
         res = link_sweep(eng, words, d, a.gap, snr, cfo_hz=a.cfo_hz, taps=None if a.taps is None else parse_taps(a.taps),
                          noise=a.noise, seed=a.seed, fading=fading, detector=a.detector, threshold=a.threshold,
-                         timing=a.timing, tracking=a.tracking, branches=a.branches, code=a.code)
+                         timing=a.timing, tracking=a.tracking, branches=a.branches, code=a.code, rate=a.rate)
     wall = time.perf_counter() - t0
     t = res["totals"]
     it = res.get("info_totals")

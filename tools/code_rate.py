@@ -9,7 +9,11 @@ events (ofdm_timing_query), reset before and read after the rounds: per launch f
 (decode) and for the stream decode kernel of the same receive call (6, 14 or 17); the gains and the Viterbi decoder
 are also given as ratios to that kernel.  Writes one JSON record under profiles/r20/code/.
 
-    python tools/code_rate.py [--packets N] [--launches K] [--out FILE]
+--rate 2/3 or 3/4 times the punctured rates' encoder and decoder instead (include/ofdm_mi355x_punct.h,
+csrc/ofdm_punct.hip), which are timed under the same ids 18 and 20; the record, under profiles/r21/punct/, then also
+holds the decoder's time per trellis step, to set against the rate-1/2 record of the same session.
+
+    python tools/code_rate.py [--packets N] [--launches K] [--rate {1/2,2/3,3/4}] [--out FILE]
 """
 from __future__ import annotations
 
@@ -31,9 +35,16 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--packets", type=int, default=1 << 16)
     ap.add_argument("--launches", type=int, default=10)
+    ap.add_argument("--rate", choices=("1/2", "2/3", "3/4"), default="1/2")
+    ap.add_argument("--branches", type=int, nargs="+", default=[1, 2], choices=(1, 2), help="the cases' B to run (default both)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
-    out = Path(a.out) if a.out else ROOT / "profiles" / "r20" / "code" / f"code_rate_{a.packets}.json"
+    if a.out:
+        out = Path(a.out)
+    elif a.rate == "1/2":
+        out = ROOT / "profiles" / "r20" / "code" / f"code_rate_{a.packets}.json"
+    else:
+        out = ROOT / "profiles" / "r21" / "punct" / f"code_rate_{a.rate.replace('/', 'of')}_{a.packets}.json"
     import torch  # noqa: PLC0415
     import ofdm_pkg  # noqa: PLC0415
     pkg = ofdm_pkg.load()
@@ -41,18 +52,18 @@ def main(argv=None) -> int:
 
     n = a.packets
     record = dict(tool="tools/code_rate.py", device=torch.cuda.get_device_name(0), packets=n, launches=a.launches,
-                  snr_db=SNR_DB, gap=GAP, cases=[])
+                  rate=a.rate, snr_db=SNR_DB, gap=GAP, cases=[])
     rng = np.random.default_rng(0xC0DE)
     with pkg.Engine(0) as eng:
-        for d, nb in CASES:
+        for d, nb in (c for c in CASES if c[1] in a.branches):
             eng.set_long_message(" " * (12 * d))
-            info = rng.integers(0, 1 << 32, (n, abi.code_info_words(d)), dtype=np.uint64).astype(np.uint32)
+            info = rng.integers(0, 1 << 32, (n, abi.punct_info_words(d, a.rate)), dtype=np.uint64).astype(np.uint32)
             tinfo = torch.from_numpy(info.view(np.int32)).cuda()
             stride = abi.packet_len(d) + GAP
             eng.timing(True)
             eng.timing_reset()
             for _ in range(a.launches + 1):
-                words = eng.encode_packets(tinfo, d)
+                words = eng.encode_packets(tinfo, d, rate=a.rate)
             enc_ms, enc_n = eng.timing_query(abi.K_CODE_ENCODE)
             clean = eng.transmit_packets(words, d, pos0=GAP, stride=stride, n_out=n * stride + GAP)
             power = float((clean.real.double() ** 2 + clean.imag.double() ** 2).sum()) / (n * abi.packet_len(d))
@@ -67,7 +78,7 @@ def main(argv=None) -> int:
                 else:
                     rx = eng.receive_diversity_device(rec, detector="conjugate", timing="ltf", tracking=tracking, want_eq=True)
                 csi = eng.stream_csi(rec if nb > 1 else rec[0], rx)
-                return rx, eng.decode_coded(rx, csi=csi)
+                return rx, eng.decode_coded(rx, csi=csi, rate=a.rate)
             round_()                                                  # warm-up
             eng.timing_reset()
             for _ in range(a.launches):
@@ -80,7 +91,9 @@ def main(argv=None) -> int:
                 per[name] = ms / cnt
             eng.timing(False)
             count = int(rx["d_count"].cpu()[1])
-            case = dict(n_data=d, branches=nb, samples=n * stride + GAP, received=count,
+            steps = abi.PUNCT_STEPS[abi.rate_code(a.rate)] * d
+            case = dict(n_data=d, branches=nb, samples=n * stride + GAP, received=count, trellis_steps=steps,
+                        code_decode_ns_per_row_step=1e6 * per["code_decode"] / (max(count, 1) * steps),
                         encode_ms=enc_ms / enc_n, stream_decode_kernel=dec_id, stream_decode_ms=per["stream_decode"],
                         stream_csi_ms=per["stream_csi"], code_decode_ms=per["code_decode"],
                         csi_over_stream_decode=per["stream_csi"] / per["stream_decode"],
@@ -91,7 +104,7 @@ def main(argv=None) -> int:
             torch.cuda.empty_cache()
     report = json.loads(build_lib.RESOURCE_REPORT.read_text())
     record["resources"] = {r["name"]: {k: r[k] for k in ("VGPRs", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")}
-                           for r in report if r.get("source") == "ofdm_code.hip"}
+                           for r in report if r.get("source") in ("ofdm_code.hip", "ofdm_punct.hip")}
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(record, indent=1))
     print(f"-> {out}", file=sys.stderr)
