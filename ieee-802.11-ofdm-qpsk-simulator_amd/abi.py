@@ -257,6 +257,34 @@ def punct_decode_lds_bytes(n_data: int, rate: str) -> int:
     return PUNCT_DECODE_WAVES * (PUNCT_STEPS[rate_code(rate)] * int(n_data) * 8 + 96 * int(n_data) * 4)
 
 
+# the extension header include/ofdm_mi355x_ppdu.h (self-describing coded packets: a header symbol that names the rate and
+# the length, 802.11a's scrambler and a CRC-32; an encoder and a fused decoder); the export lists above and ABI_VERSION do
+# not change with it
+PPDU_HEADER = PKG_DIR.parent / "include" / "ofdm_mi355x_ppdu.h"
+_PPDU_SIGS = {
+    "ofdm_ppdu_encode": (C.c_int, [_V, C.c_int32, _V, _V, _V, _V, C.c_int64, _V, _V]),
+    "ofdm_ppdu_decode": (C.c_int, [_V, C.c_int32, _V, _V, _V, C.c_int64, _V, _V, _V]),
+}
+PPDU_FUNCTIONS = tuple(_PPDU_SIGS)                # not named *_EXPORTS: like the lists since the diversity header's
+PPDU_MIN_SYMBOLS = 2                             # OFDM_PPDU_MIN_SYMBOLS: the header's symbol and one data symbol
+PPDU_PSDU_WORDS, PPDU_INFO_WORDS = 31, 36        # OFDM_PPDU_PSDU_WORDS, OFDM_PPDU_INFO_WORDS
+PPDU_SERVICE_BITS, PPDU_MIN_LENGTH = 16, 4       # OFDM_PPDU_SERVICE_BITS, OFDM_PPDU_MIN_LENGTH
+PPDU_BAD_HEADER, PPDU_BAD_SERVICE, PPDU_BAD_FCS = 1, 2, 4       # OFDM_PPDU_BAD_*: d_meta's status bits
+PPDU_DECODE_WAVES = 2                            # PPDU_WAVES (csrc/ofdm_ppdu.hip): rows per block and sweep
+
+
+def ppdu_cap(n_data: int, rate: str) -> int:
+    """cap(D, rate): the largest LENGTH of a packet of D symbols, (S (D - 1) - 6 - 16) // 8"""
+    return (punct_info_bits(int(n_data) - 1, rate) - PPDU_SERVICE_BITS) // 8
+
+
+def ppdu_decode_lds_bytes(n_data: int) -> int:
+    """The fused decode kernel's dynamic LDS per block: per wave 72 (D - 1) 64-bit words (the data part's decisions at the
+    worst rate; at least 96, since the header's 48 decisions and 96 soft values lie there first) and the data symbols'
+    96 (D - 1) soft values as floats, 13,440 bytes at D = 15; it has no static LDS."""
+    return PPDU_DECODE_WAVES * (max(72 * (int(n_data) - 1), 96) * 8 + 96 * (int(n_data) - 1) * 4)
+
+
 class OfdmError(RuntimeError):
     pass
 
@@ -474,7 +502,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib = C.CDLL(str(p))
     for name, (res, args) in {**_SIGS, **_LONG_SIGS, **_CAPTURES_SIGS, **_STREAM_SIGS, **_TX_SIGS,
                               **_CHANNEL_SIGS, **_FADING_SIGS, **_DETECT_SIGS, **_TIMING_SIGS, **_TRACK_SIGS,
-                              **_DIVERSITY_SIGS, **_CODE_SIGS, **_PUNCT_SIGS}.items():
+                              **_DIVERSITY_SIGS, **_CODE_SIGS, **_PUNCT_SIGS, **_PPDU_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

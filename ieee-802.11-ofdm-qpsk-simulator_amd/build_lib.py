@@ -22,7 +22,7 @@ SOURCES = ["ofdm_capi.hip", "ofdm_symbol.hip", "ofdm_rxpack.hip", "ofdm_rxpack_i
            "ofdm_frame_sym.hip", "ofdm_frame_fix.hip", "ofdm_frame_long.hip", "ofdm_frame_xl.hip",
            "ofdm_captures.hip", "ofdm_stream.hip", "ofdm_transmit.hip", "ofdm_channel.hip", "ofdm_fading.hip",
            "ofdm_stream_conj.hip", "ofdm_stream_timing.hip", "ofdm_stream_track.hip", "ofdm_stream_div.hip", "ofdm_code.hip",
-           "ofdm_punct.hip"]
+           "ofdm_punct.hip", "ofdm_ppdu.hip"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: keep f32 math scalar (packed v_pk_* f32 gives no rate on gfx950 and its
@@ -44,7 +44,8 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vecto
 # the packet transmitter (ofdm_transmit.hip), the channel and scoring kernels (ofdm_channel.hip) and the fading
 # transmitter (ofdm_fading.hip), the stream receiver's optional detectors (ofdm_stream_conj.hip), its fine timing
 # kernel (ofdm_stream_timing.hip), its pilot-tracking decode (ofdm_stream_track.hip), its diversity kernels
-# (ofdm_stream_div.hip), the coded link's kernels (ofdm_code.hip) and its punctured rates (ofdm_punct.hip).
+# (ofdm_stream_div.hip), the coded link's kernels (ofdm_code.hip), its punctured rates (ofdm_punct.hip) and its
+# self-describing packets (ofdm_ppdu.hip; -DOFDM_PPDU_CRC_BITWISE builds the decoder's FCS without its byte table).
 SOURCE_FLAGS = {"ofdm_symbol.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 "ofdm_rxpack.hip": os.environ.get("OFDM_RXPACK_FLAGS", "-mllvm -amdgpu-sched-strategy=max-ilp").split(),
                 "ofdm_rxpack_ideal.hip": os.environ.get("OFDM_RXPACK_IDEAL_FLAGS", "").split(),
@@ -65,7 +66,8 @@ SOURCE_FLAGS = {"ofdm_symbol.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 "ofdm_stream_track.hip": os.environ.get("OFDM_STREAM_TRACK_FLAGS", "").split(),
                 "ofdm_stream_div.hip": os.environ.get("OFDM_STREAM_DIV_FLAGS", "").split(),
                 "ofdm_code.hip": os.environ.get("OFDM_CODE_FLAGS", "").split(),
-                "ofdm_punct.hip": os.environ.get("OFDM_PUNCT_FLAGS", "").split()}
+                "ofdm_punct.hip": os.environ.get("OFDM_PUNCT_FLAGS", "").split(),
+                "ofdm_ppdu.hip": os.environ.get("OFDM_PPDU_FLAGS", "").split()}
 
 
 # Kernels whose parity-dump variants (last template argument `true`) are allowed to spill: they

@@ -861,6 +861,99 @@ class Engine:
                                                        opt(path)), "punct_decode")
         return dict(d_info=info, d_path=path, frames=nd)
 
+    # ---- self-describing packets (include/ofdm_mi355x_ppdu.h) -----------------------------
+    def encode_ppdu(self, psdu, lengths, rates, seeds, n_data: int) -> dict:
+        """PSDUs -> payload words on the device (ofdm_ppdu_encode; stream.ppdu_encode is the rule): per packet a header
+        symbol that names rate and LENGTH, the FCS over the first LENGTH - 4 bytes written behind them, the scrambler
+        from the packet's seed, and the K = 7 code at the packet's rate.  psdu: 32-bit words [n, 31]; lengths, rates
+        (codes 0, 1, 2 for "1/2", "2/3", "3/4") and seeds (1 .. 127): integers [n]; each a numpy array (uploaded) or a
+        contiguous int32 tensor on this engine's device.  n_data: D symbols per packet, the header's among them, 2 .. 15.
+        Host arrays are checked here: ValueError for a rate outside 0 .. 2, a LENGTH outside [4, abi.ppdu_cap(D, rate)]
+        or a seed outside [1, 127].  Device tensors cannot be checked without a synchronisation: the kernel sends such a
+        packet with a header that no receiver accepts (LENGTH 0 under a RATE field of 0).  Returns d_words (int32
+        [n, 3 D], what transmit_packets and transmit_faded take) and d_info (int32 [n, 36], the header words and the
+        scrambled information words).  Nothing waits for the device."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        nd = int(n_data)
+        if nd != n_data or not abi.PPDU_MIN_SYMBOLS <= nd <= abi.LONG_MAX_DATA_SYMBOLS:
+            raise ValueError(f"n_data must be in [{abi.PPDU_MIN_SYMBOLS}, {abi.LONG_MAX_DATA_SYMBOLS}], got {n_data!r}")
+        host = [np.asarray(x).reshape(-1) for x in (lengths, rates, seeds) if not torch.is_tensor(x)]
+        if len(host) == 3:
+            ln, rt, sd = (x.astype(np.int64) for x in host)
+            if not (len(ln) == len(rt) == len(sd)):
+                raise ValueError(f"lengths, rates and seeds must have one entry per packet, got {len(ln)}, {len(rt)}, {len(sd)}")
+            if ((rt < 0) | (rt > 2)).any():
+                raise ValueError(f"a rate code must be 0, 1 or 2, got {rt[(rt < 0) | (rt > 2)][0]}")
+            caps = np.array([abi.ppdu_cap(nd, r) for r in abi.RATE])[rt]
+            bad = (ln < abi.PPDU_MIN_LENGTH) | (ln > caps)
+            if bad.any():
+                k = int(np.nonzero(bad)[0][0])
+                raise ValueError(f"packet {k}: LENGTH must be in [{abi.PPDU_MIN_LENGTH}, {caps[k]}] for {nd} symbols at rate "
+                                 f"{tuple(abi.RATE)[rt[k]]}, got {ln[k]}")
+            if ((sd < 1) | (sd > 127)).any():
+                raise ValueError(f"a seed must be in [1, 127], got {sd[(sd < 1) | (sd > 127)][0]}")
+        if isinstance(psdu, np.ndarray):
+            if psdu.dtype not in (np.uint32, np.int32) or psdu.ndim != 2:
+                raise ValueError(f"psdu must be uint32 [n, {abi.PPDU_PSDU_WORDS}], got {psdu.dtype} {psdu.shape}")
+            psdu = torch.from_numpy(np.ascontiguousarray(psdu).view(np.int32)).to(dev)
+        if not torch.is_tensor(psdu) or psdu.dtype != torch.int32 or psdu.dim() != 2 or psdu.shape[1] != abi.PPDU_PSDU_WORDS:
+            raise ValueError(f"psdu must be 32-bit integers [n, {abi.PPDU_PSDU_WORDS}]")
+        n = int(psdu.shape[0])
+        per = []
+        for name, x in (("lengths", lengths), ("rates", rates), ("seeds", seeds)):
+            if not torch.is_tensor(x):
+                x = torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1).astype(np.int32))).to(dev)
+            if x.dtype != torch.int32 or tuple(x.shape) != (n,):
+                raise ValueError(f"{name} must be int32 [{n}]")
+            per.append(x)
+        for x in (psdu, *per):
+            if x.device != dev or not x.is_contiguous():
+                raise ValueError(f"psdu, lengths, rates and seeds must be contiguous on {dev}")
+        info = torch.empty((n, abi.PPDU_INFO_WORDS), dtype=torch.int32, device=dev)
+        words = torch.empty((n, 3 * nd), dtype=torch.int32, device=dev)
+        if n:
+            check(self.lib, self.lib.ofdm_ppdu_encode(self.ctx, nd, _ptr(psdu), _ptr(per[0]), _ptr(per[1]), _ptr(per[2]), n,
+                                                      _ptr(info), _ptr(words)), "ppdu_encode")
+        return dict(d_words=words, d_info=info, frames=nd)
+
+    def decode_ppdu(self, rx, csi=None, want_path: bool = False, n_data: int | None = None) -> dict:
+        """The fused decoder of self-describing packets (ofdm_ppdu_decode; stream.ppdu_decode is the rule, bit for bit):
+        per row the header symbol, then the data symbols at the rate the header names, the descrambling and the FCS.
+        rx, csi, n_data: decode_coded's.  Returns d_meta (int32 [rows, 4]: status -- 0 for a packet whose FCS passed,
+        else abi.PPDU_BAD_* bits --, the rate's code or -1, LENGTH, seed), d_psdu (int32 [rows, 31], MSB first: the LENGTH
+        bytes, zeros behind) and d_path (float32 [rows, 2], the header's and the data part's path metric; None without
+        want_path).  With rx a result, the first d_count[1] rows are written.  Nothing waits for the device."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        if isinstance(rx, dict):
+            eq, cnt = rx.get("d_eq"), rx["d_count"]
+            if eq is None:
+                raise ValueError("the receive call must be made with want_eq=True")
+        else:
+            eq, cnt = rx, None
+        if not torch.is_tensor(eq) or eq.dtype != torch.complex64 or eq.dim() != 2 or eq.shape[1] % 48:
+            raise ValueError("d_eq must be a complex64 tensor [n, 48 D]")
+        if eq.device != dev or not eq.is_contiguous():
+            raise ValueError(f"d_eq must be contiguous on {dev}")
+        n, nd = int(eq.shape[0]), int(eq.shape[1]) // 48
+        if n_data is not None and int(n_data) != nd:
+            raise ValueError(f"d_eq holds {nd} symbols per row, n_data is {n_data}")
+        if not abi.PPDU_MIN_SYMBOLS <= nd <= abi.LONG_MAX_DATA_SYMBOLS:
+            raise ValueError(f"{abi.PPDU_MIN_SYMBOLS} to {abi.LONG_MAX_DATA_SYMBOLS} symbols per row expected, got {nd}")
+        if csi is not None:
+            if not (torch.is_tensor(csi) and csi.dtype == torch.float32 and csi.device == dev and csi.is_contiguous()
+                    and tuple(csi.shape) == (n, 48)):
+                raise ValueError(f"csi must be a contiguous float32 device tensor [{n}, 48]")
+        meta = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        psdu = torch.empty((n, abi.PPDU_PSDU_WORDS), dtype=torch.int32, device=dev)
+        path = torch.empty((n, 2), dtype=torch.float32, device=dev) if want_path else None
+        opt = lambda x: None if x is None else _ptr(x)
+        if n:
+            check(self.lib, self.lib.ofdm_ppdu_decode(self.ctx, nd, _ptr(eq), opt(csi), opt(cnt), n, _ptr(meta), _ptr(psdu),
+                                                      opt(path)), "ppdu_decode")
+        return dict(d_meta=meta, d_psdu=psdu, d_path=path, frames=nd)
+
     @staticmethod
     def _div_max_packets(n: int, max_packets) -> int:
         if max_packets is None:

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import argparse
 import csv
+import functools
 import sys
 from pathlib import Path
 
@@ -689,6 +690,283 @@ def viterbi_decode_rate(soft, rate: str = "1/2") -> dict:
         raise ValueError(f"soft float32 [n, {s2} D] with 1 <= D <= {MAX_DATA_SYMBOLS} expected at rate {rate}, got "
                          f"{lam.dtype} {lam.shape}")
     return _viterbi(lam)
+
+
+# ---- self-describing packets (include/ofdm_mi355x_ppdu.h): a header symbol, 802.11a's scrambler and a CRC-32 ----
+PPDU_PSDU_WORDS = 31      # OFDM_PPDU_PSDU_WORDS: 124 bytes >= ppdu_cap(15, "3/4")
+PPDU_INFO_WORDS = 36      # OFDM_PPDU_INFO_WORDS: the 2 header words and room for 34 more (rate_info_words(14, "3/4") = 32 in use)
+PPDU_HEADER_BITS = 42     # INFO_BITS(1): the header symbol is a one-symbol rate-1/2 packet
+PPDU_SERVICE_BITS = 16
+PPDU_MIN_LENGTH = 4       # the FCS alone
+PPDU_BAD_HEADER, PPDU_BAD_SERVICE, PPDU_BAD_FCS = 1, 2, 4       # OFDM_PPDU_BAD_*: the status bits
+PPDU_MIN_DATA_SYMBOLS = 2
+
+
+def scramble_sequence(seed: int, n: int) -> np.ndarray:
+    """The first n output bits of 802.11a's scrambler x^7 + x^4 + 1 from the state `seed` (1 .. 127, x7 the top bit):
+    per bit out = x7 ^ x4, shifted in at x1.  uint8 [n]; the period is 127."""
+    s = int(seed)
+    if s != seed or not 1 <= s <= 127:
+        raise ValueError(f"seed must be in [1, 127], got {seed!r}")
+    return np.resize(_scramble_period(s), int(n))
+
+
+@functools.lru_cache(maxsize=None)
+def _scramble_period(s: int) -> np.ndarray:
+    out = np.zeros(127, np.uint8)
+    for k in range(127):
+        b = ((s >> 6) ^ (s >> 3)) & 1
+        out[k] = b
+        s = ((s << 1) | b) & 127
+    out.setflags(write=False)
+    return out
+
+
+def fcs32(data) -> int:
+    """The frame check sequence of a body (bytes): CRC-32 as zlib.crc32 computes it, bit by bit -- reflected polynomial
+    0xEDB88320, the register starts at 0xFFFFFFFF, a byte enters at the low end, the result is complemented."""
+    c = 0xFFFFFFFF
+    for byte in bytes(data):
+        c ^= byte
+        for _ in range(8):
+            c = (c >> 1) ^ (0xEDB88320 if c & 1 else 0)
+    return c ^ 0xFFFFFFFF
+
+
+def crc8(bits) -> int:
+    """The header's CRC-8 over a bit sequence: c = 0xFF; per bit b, f = b ^ (c >> 7), c = ((c << 1) & 0xFF) ^ (7 if f
+    else 0); the field is ~c."""
+    c = 0xFF
+    for b in bits:
+        f = (int(b) & 1) ^ (c >> 7)
+        c = ((c << 1) & 0xFF) ^ (0x07 if f else 0)
+    return c ^ 0xFF
+
+
+def _ppdu_n_data(n_data) -> int:
+    d = int(n_data)
+    if d != n_data or not PPDU_MIN_DATA_SYMBOLS <= d <= MAX_DATA_SYMBOLS:
+        raise ValueError(f"n_data must be in [{PPDU_MIN_DATA_SYMBOLS}, {MAX_DATA_SYMBOLS}] (a header symbol and at least one "
+                         f"data symbol), got {n_data!r}")
+    return d
+
+
+def _ppdu_rate(rate) -> str:
+    """a rate as "1/2", "2/3", "3/4" or as its code 0, 1, 2"""
+    if isinstance(rate, (int, np.integer)) and not isinstance(rate, bool) and 0 <= int(rate) < len(RATES):
+        return RATES[int(rate)]
+    return _rate(rate)
+
+
+def ppdu_cap(n_data: int, rate: str) -> int:
+    """The largest LENGTH (PSDU bytes, the four FCS bytes among them) of a packet of D symbols at a rate:
+    (S (D - 1) - 6 - 16) // 8.  D = 2 at rate 1/2 gives 3, under the smallest LENGTH of 4."""
+    return (rate_info_bits(_ppdu_n_data(n_data) - 1, _ppdu_rate(rate)) - PPDU_SERVICE_BITS) // 8
+
+
+def _ppdu_header_bits(rate_field: int, length: int) -> np.ndarray:
+    b = np.zeros(PPDU_HEADER_BITS, np.uint8)
+    b[0:4] = [(rate_field >> (3 - k)) & 1 for k in range(4)]
+    b[5:17] = [(length >> (11 - k)) & 1 for k in range(12)]
+    b[17] = b[:17].sum() & 1
+    c = crc8(b[:18])
+    b[18:26] = [(c >> (7 - k)) & 1 for k in range(8)]
+    return b
+
+
+def ppdu_header(rate, length: int) -> np.ndarray:
+    """The 42 header bits as 2 words, MSB first: RATE = 5 + the rate's code in bits 0..3, bit 4 zero, LENGTH in bits 5..16,
+    even parity over bits 0..16 in bit 17, crc8 of bits 0..17 in bits 18..25, zeros to bit 41.  LENGTH is any 12-bit
+    value: ppdu_encode is what refuses one a packet cannot hold."""
+    ln = int(length)
+    if ln != length or not 0 <= ln < 4096:
+        raise ValueError(f"length must be in [0, 4095], got {length!r}")
+    return _pack_bits(_ppdu_header_bits(5 + RATES.index(_ppdu_rate(rate)), ln)[None])[0]
+
+
+def ppdu_header_check(words, n_data: int | None = None):
+    """(valid, rate, length) of header words uint32 [n, 2] (or [2]): valid iff RATE is 5, 6 or 7, bit 4 is 0, the parity
+    and the CRC-8 are right, bits 26..41 are zero and, with n_data, 4 <= LENGTH <= ppdu_cap(n_data, rate).  rate is the
+    rate's code (int32, -1 where invalid) and length int32 (0 where invalid)."""
+    w = np.asarray(words).astype(np.uint32, copy=False)
+    single = w.ndim == 1
+    w = np.ascontiguousarray(w.reshape(-1, 2))
+    bits = np.unpackbits(w.astype(">u4").view(np.uint8), axis=1)
+    field = bits[:, 0:4] @ (8, 4, 2, 1)
+    length = (bits[:, 5:17].astype(np.int64) @ (1 << np.arange(11, -1, -1))).astype(np.int64)
+    crc = np.full(len(bits), 0xFF, np.int64)                          # crc8 of bits 0..17, all rows at once
+    for k in range(18):
+        f = bits[:, k] ^ (crc >> 7)
+        crc = ((crc << 1) & 0xFF) ^ (0x07 * f)
+    crc ^= 0xFF
+    valid = (field >= 5) & (field <= 7) & (bits[:, 4] == 0) & (bits[:, :18].sum(axis=1) % 2 == 0)
+    valid &= (bits[:, 18:26] @ (1 << np.arange(7, -1, -1))) == crc
+    valid &= ~bits[:, 26:].any(axis=1)
+    valid &= length >= PPDU_MIN_LENGTH
+    if n_data is not None:
+        caps = np.array([ppdu_cap(n_data, r) for r in RATES])
+        valid &= length <= caps[np.clip(field - 5, 0, 2)]
+    rate = np.where(valid, field - 5, -1).astype(np.int32)
+    length = np.where(valid, length, 0).astype(np.int32)
+    return (bool(valid[0]), int(rate[0]), int(length[0])) if single else (valid, rate, length)
+
+
+def ppdu_fill(psdu_words, lengths) -> np.ndarray:
+    """The PSDUs as they are sent: uint32 [n, 31] with, per row, the first LENGTH - 4 bytes of psdu_words (MSB first),
+    their fcs32 big-endian in the next four and zeros behind; whatever psdu_words hold from byte LENGTH - 4 on is
+    ignored."""
+    w = np.ascontiguousarray(np.asarray(psdu_words).astype(np.uint32, copy=False))
+    ln = np.asarray(lengths, np.int64).reshape(-1)
+    if w.ndim != 2 or w.shape[1] != PPDU_PSDU_WORDS or len(ln) != len(w):
+        raise ValueError(f"psdu words [n, {PPDU_PSDU_WORDS}] and n lengths expected, got {w.shape} and {ln.shape}")
+    if len(ln) and (ln.min() < PPDU_MIN_LENGTH or ln.max() > 4 * PPDU_PSDU_WORDS):
+        raise ValueError(f"a LENGTH must be in [{PPDU_MIN_LENGTH}, {4 * PPDU_PSDU_WORDS}]")
+    by = w.astype(">u4").view(np.uint8).reshape(len(w), 4 * PPDU_PSDU_WORDS).copy()
+    # fcs32 of every row's body at once: the rule's eight steps per byte folded into a table, one byte column at a time
+    table = np.arange(256, dtype=np.uint32)
+    for _ in range(8):
+        table = (table >> 1) ^ np.where(table & 1, np.uint32(0xEDB88320), np.uint32(0))
+    crc = np.full(len(w), 0xFFFFFFFF, np.uint32)
+    for j in range(int(ln.max()) - 4 if len(ln) else 0):
+        crc = np.where(j < ln - 4, (crc >> 8) ^ table[(crc ^ by[:, j]) & 0xFF], crc)
+    crc ^= np.uint32(0xFFFFFFFF)
+    col = np.arange(by.shape[1])[None, :]
+    k = col - (ln[:, None] - 4)                                      # 0..3 in the FCS's place
+    fcs = (crc[:, None] >> (8 * (3 - np.clip(k, 0, 3))).astype(np.uint32)) & 0xFF
+    by = np.where(k < 0, by, np.where(k < 4, fcs, 0)).astype(np.uint8)
+    return np.ascontiguousarray(by).view(">u4").astype(np.uint32)
+
+
+def ppdu_encode(psdu_words, lengths, rates, seeds, n_data: int, strict: bool = True):
+    """The encoder of include/ofdm_mi355x_ppdu.h, its executable specification.  psdu_words: uint32 [n, 31]; lengths, rates
+    (codes 0..2 or "1/2", "2/3", "3/4") and seeds (1..127): one per packet; n_data: D symbols, the header's among them.
+    Returns (payload words uint32 [n, 3 D], info words uint32 [n, 36]).  An info row holds the 2 header words and then the
+    data part's W_i = rate_info_words(D - 1, rate) words: 16 SERVICE zeros, the ppdu_fill PSDU and zeros up to K =
+    rate_info_bits(D - 1, rate) bits, all K XORed with scramble_sequence(seed, K); the rest of the row is 0.  The payload
+    is conv_encode_rate(header, 1, "1/2") followed by conv_encode_rate(data, D - 1, rate).
+    ValueError for a LENGTH outside [4, ppdu_cap], a seed outside [1, 127] or an unknown rate.  strict=False is the
+    device encoder's rule for such a packet instead: LENGTH 0 under a RATE field of 0, which no receiver takes for a
+    header, and an all-zero data part at rate 1/2."""
+    d = _ppdu_n_data(n_data)
+    w = np.ascontiguousarray(np.asarray(psdu_words).astype(np.uint32, copy=False))
+    n = len(w)
+    if w.ndim != 2 or w.shape[1] != PPDU_PSDU_WORDS:
+        raise ValueError(f"psdu words [n, {PPDU_PSDU_WORDS}] expected, got {w.shape}")
+    ln = np.asarray(lengths).reshape(-1)
+    sd = np.asarray(seeds).reshape(-1)
+    rt = list(rates) if not isinstance(rates, (str, int, np.integer)) else [rates] * n
+    if not (len(ln) == len(sd) == len(rt) == n):
+        raise ValueError(f"{n} lengths, rates and seeds expected, got {len(ln)}, {len(rt)} and {len(sd)}")
+    info = np.zeros((n, PPDU_INFO_WORDS), np.uint32)
+    words = np.zeros((n, 3 * d), np.uint32)
+    code = np.full(n, -1)                                            # -1: a refused packet (strict=False)
+    for i in range(n):
+        try:
+            rate = _ppdu_rate(rt[i])
+            if int(ln[i]) != ln[i] or not PPDU_MIN_LENGTH <= int(ln[i]) <= ppdu_cap(d, rate):
+                raise ValueError(f"packet {i}: LENGTH must be in [{PPDU_MIN_LENGTH}, {ppdu_cap(d, rate)}] for {d} symbols "
+                                 f"at rate {rate}, got {ln[i]!r}")
+            if int(sd[i]) != sd[i] or not 1 <= int(sd[i]) <= 127:
+                raise ValueError(f"packet {i}: seed must be in [1, 127], got {sd[i]!r}")
+        except ValueError:
+            if strict:
+                raise
+            info[i, :2] = _pack_bits(_ppdu_header_bits(0, 0)[None])[0]
+            continue
+        k, wi = rate_info_bits(d - 1, rate), rate_info_words(d - 1, rate)
+        bits = np.zeros(k, np.uint8)
+        body = ppdu_fill(w[i:i + 1], [int(ln[i])])
+        bits[16:16 + 8 * int(ln[i])] = np.unpackbits(body.astype(">u4").view(np.uint8))[:8 * int(ln[i])]
+        bits ^= scramble_sequence(int(sd[i]), k)
+        info[i, :2] = ppdu_header(rate, int(ln[i]))
+        info[i, 2:2 + wi] = _pack_bits(bits[None])[0]
+        code[i] = RATES.index(rate)
+    words[:, :3] = conv_encode_rate(info[:, :2], 1, "1/2")
+    for c, rate in enumerate(RATES):
+        rows = np.nonzero(code == c)[0]
+        words[rows, 3:] = conv_encode_rate(info[rows, 2:2 + rate_info_words(d - 1, rate)], d - 1, rate)
+    return words, info
+
+
+def _scrambler_seed(state7: int) -> int:
+    """the seed whose first seven output bits are `state7`, MSB first: seven steps of the register backwards (0 for 0)"""
+    s = int(state7)
+    for _ in range(7):
+        s = (s >> 1) | (((s & 1) ^ ((s >> 4) & 1)) << 6)
+    return s
+
+
+def ppdu_decode(eq, csi=None) -> dict:
+    """The decoder of include/ofdm_mi355x_ppdu.h in fp32, its executable specification.  eq: complex [n, 48 D], 2 <= D <= 15;
+    csi: [n, 48] or None.  Columns [0, 48) are decoded as a one-symbol rate-1/2 packet (conv_soft_rate,
+    viterbi_decode_rate) and checked (ppdu_header_check with D).  A row whose header fails gets status PPDU_BAD_HEADER,
+    rate -1, length 0, seed 0, a zero psdu and path[1] = 0.  Otherwise columns [48, 48 D) are decoded at the header's rate
+    with the same gains; the first seven decoded bits are the scrambler's state, from which the seed (seven steps back)
+    and the sequence follow -- seven zeros are no state: seed 0, nothing descrambled, PPDU_BAD_SERVICE; descrambled bits
+    7..15 other than zero are PPDU_BAD_SERVICE as well; the psdu is the LENGTH bytes behind the 16 SERVICE bits, zeros
+    after them; PPDU_BAD_FCS unless its last four bytes are fcs32 of the ones before.
+    Returns status, rate, length, seed (int32 [n]), psdu (uint32 [n, 31]) and path (float32 [n, 2]: header, data)."""
+    z = np.asarray(eq).astype(np.complex64)
+    if z.ndim != 2 or z.shape[1] % 48 or not PPDU_MIN_DATA_SYMBOLS <= z.shape[1] // 48 <= MAX_DATA_SYMBOLS:
+        raise ValueError(f"eq [n, 48 D] with {PPDU_MIN_DATA_SYMBOLS} <= D <= {MAX_DATA_SYMBOLS} expected, got {z.shape}")
+    n, d = len(z), z.shape[1] // 48
+    head = viterbi_decode_rate(conv_soft_rate(z[:, :48], csi, "1/2"), "1/2")
+    valid, rate, length = ppdu_header_check(head["info"], d) if n else (np.zeros(0, bool),) * 3
+    status = np.where(valid, 0, PPDU_BAD_HEADER).astype(np.int32)
+    seed = np.zeros(n, np.int32)
+    psdu = np.zeros((n, PPDU_PSDU_WORDS), np.uint32)
+    path = np.zeros((n, 2), np.float32)
+    path[:, 0] = head["path"]
+    w = None if csi is None else np.asarray(csi)
+    for code, name in enumerate(RATES):
+        rows = np.nonzero(valid & (rate == code))[0]
+        if not len(rows):
+            continue
+        k = rate_info_bits(d - 1, name)
+        out = viterbi_decode_rate(conv_soft_rate(z[rows, 48:], None if w is None else w[rows], name), name)
+        path[rows, 1] = out["path"]
+        bits = np.unpackbits(out["info"].astype(">u4").view(np.uint8), axis=1)[:, :k]
+        state = bits[:, :7] @ (64, 32, 16, 8, 4, 2, 1)
+        seed[rows] = [_scrambler_seed(v) for v in state]
+        sequences = np.zeros((128, k), np.uint8)                      # row 0: seven zeros are no state
+        for v in set(seed[rows].tolist()) - {0}:
+            sequences[v] = scramble_sequence(v, k)
+        bits = bits ^ sequences[seed[rows]]
+        status[rows[(state == 0) | bits[:, 7:16].any(axis=1)]] |= PPDU_BAD_SERVICE
+        body = np.zeros((len(rows), 8 * 4 * PPDU_PSDU_WORDS), np.uint8)
+        room = min(k - 16, body.shape[1])
+        body[:, :room] = bits[:, 16:16 + room]
+        body[np.arange(body.shape[1])[None, :] >= 8 * length[rows, None]] = 0
+        by = np.packbits(body, axis=1)
+        psdu[rows] = np.ascontiguousarray(by).view(">u4").astype(np.uint32)
+        for i, row, ln in zip(rows, by, length[rows]):
+            if int.from_bytes(row[ln - 4:ln].tobytes(), "big") != fcs32(row[:ln - 4].tobytes()):
+                status[i] |= PPDU_BAD_FCS
+    return dict(status=status, rate=rate, length=length, seed=seed, psdu=psdu, path=path)
+
+
+def pack_ppdu_messages(texts, n_data: int | None = None, rate="1/2"):
+    """One packet per text for ppdu_encode: (psdu words uint32 [n, 31], lengths int32 [n], D).  A text (str, latin-1, or
+    bytes) is the PSDU's body, so LENGTH = len + 4; rate is one rate or one per text.  D is n_data, or the smallest
+    number of symbols that holds every text at its rate.  ValueError for a text that needs more than 15 symbols or
+    more than n_data."""
+    rows = [t.encode("latin-1") if isinstance(t, str) else bytes(t) for t in texts]
+    rates = [_ppdu_rate(rate)] * len(rows) if isinstance(rate, (str, int, np.integer)) else [_ppdu_rate(r) for r in rate]
+    if len(rates) != len(rows):
+        raise ValueError(f"{len(rows)} rates expected, got {len(rates)}")
+    need = [next((d for d in range(PPDU_MIN_DATA_SYMBOLS, MAX_DATA_SYMBOLS + 1) if ppdu_cap(d, r) >= len(b) + 4), None)
+            for b, r in zip(rows, rates)]
+    for b, r, k in zip(rows, rates, need):
+        if k is None:
+            raise ValueError(f"a text of {len(b)} characters does not fit a packet at rate {r}: {MAX_DATA_SYMBOLS} symbols "
+                             f"carry at most {ppdu_cap(MAX_DATA_SYMBOLS, r) - 4}")
+    d = max(need, default=PPDU_MIN_DATA_SYMBOLS) if n_data is None else _ppdu_n_data(n_data)
+    if need and max(need) > d:
+        raise ValueError(f"a text needs {max(need)} symbols, n_data is {d}")
+    buf = np.zeros((len(rows), 4 * PPDU_PSDU_WORDS), np.uint8)
+    for k, b in enumerate(rows):
+        buf[k, :len(b)] = np.frombuffer(b, np.uint8)
+    return buf.view(">u4").astype(np.uint32), np.array([len(b) + 4 for b in rows], np.int32), d
 
 
 def rrc_taps() -> np.ndarray:

@@ -176,7 +176,8 @@ def captures_main(argv=None):
 def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: float = 0.0, taps=None,
                noise: str = "real", seed: int = 0x80211A, trial: int = 0, window=None, fading=None,
                detector: str = "reference", threshold: float = 0.75, timing: str = "none",
-               tracking: str = "none", branches: int = 1, code: str | None = None, rate: str = "1/2") -> dict:
+               tracking: str = "none", branches: int = 1, code: str | None = None, rate="1/2", lengths=None,
+               keep_packets: bool = False) -> dict:
     """Packet-error and bit-error counts against SNR for packets that each carry their own bits, the recording never
     leaving the device: the packets (words: uint32 [n, 3 n_data], each behind `gap` idle samples, and a closing gap)
     are transmitted once; per SNR point q the clean recording is impaired into a second buffer with the noise stream
@@ -217,6 +218,17 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
     DESIGN.md K21): `words` are then [n, abi.punct_info_words(n_data, rate)], S D - 6 information bits per packet with
     S = 64 or 72, and the encoder and decoder are the punctured ones; info_totals keep their meaning.  With "1/2" every
     call is what it was without the argument.
+    code="ppdu" (include/ofdm_mi355x_ppdu.h): self-describing packets of n_data symbols, the header's among
+    them.  `words` are PSDU words [n, 31]; rate is one rate, a sequence of n rates, or "mixed" (packet i at rate code
+    i mod 3); lengths gives the LENGTH values (the FCS's four bytes among them) and defaults to every packet's
+    abi.ppdu_cap; packet i's scrambler seed is 1 + (i mod 127).  Engine.encode_ppdu makes the payload words once, and per
+    SNR point Engine.decode_ppdu reads rate and LENGTH off every record's header, decodes, descrambles and checks the
+    FCS.  The result then also holds ppdu_totals (int64 [n_snr, 3, 5]), counted on the device per rate of the sent
+    packet among the matched ones: matched; header valid with the sent rate and LENGTH; FCS passed (status 0, what a
+    receiver sees without knowing what was sent); FCS passed but the PSDU differs from the sent one; PSDU bit errors among
+    the header-right packets.  keep_packets=True adds ppdu_packets, per SNR point (meta int32 [n, 4], psdu uint32
+    [n, 31], matched bool [n]) of the record matched to every sent packet.  totals are those of the payload words, as
+    with code=None on the same words.
 
     Returns snr_db, totals (int64 [n_snr, NSCORE]), power, packets, samples."""
     import torch  # noqa: PLC0415
@@ -241,14 +253,28 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
         raise ValueError(f"gap must not be negative, got {gap}")
     if gap < window[1]:
         raise ValueError(f"gap {gap} is shorter than the scoring window {tuple(window)}: a record could serve two packets")
-    if code not in (None, "conv"):
-        raise ValueError(f"code must be None or 'conv', got {code!r}")
-    if abi.rate_code(rate) and not code:
-        raise ValueError(f"rate {rate!r} needs code='conv'")
+    if code not in (None, "conv", "ppdu"):
+        raise ValueError(f"code must be None, 'conv' or 'ppdu', got {code!r}")
+    if code == "ppdu":
+        ppdu = _ppdu_plan(words, n_data, rate, lengths)              # ValueError before anything is set or launched
+    else:
+        if lengths is not None or keep_packets:
+            raise ValueError("lengths and keep_packets need code='ppdu'")
+        if abi.rate_code(rate) and not code:
+            raise ValueError(f"rate {rate!r} needs code='conv'")
     set_message(engine, " " * (12 * n_data))
     dev = torch.device("cuda", engine.device)
-    w = words if torch.is_tensor(words) else torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(dev)
-    if code:
+    if code == "ppdu":
+        w = engine.encode_ppdu(ppdu["psdu"], ppdu["lengths"], ppdu["rates"], ppdu["seeds"], n_data)["d_words"]
+        sent = torch.from_numpy(ppdu["sent"].view(np.int32)).to(dev)
+        sent_rate = torch.from_numpy(ppdu["rates"].astype(np.int64)).to(dev)
+        sent_len = torch.from_numpy(ppdu["lengths"].astype(np.int32)).to(dev)
+        popcount = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int64, device=dev)
+        ppdu_totals = torch.zeros((len(snr), 3, 5), dtype=torch.int64, device=dev)
+        kept = []
+    else:
+        w = words if torch.is_tensor(words) else torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(dev)
+    if code == "conv":
         # the sent information words without the last word's unused bits (the decoder writes them as 0), then the payload
         wi, kinfo = abi.punct_info_words(n_data, rate), abi.punct_info_bits(n_data, rate)
         if w.dim() != 2 or w.shape[1] != wi:
@@ -295,6 +321,20 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
         else:
             rx = engine.receive_diversity_device(rec, detector=detector, threshold=threshold, timing=timing, tracking=tracking,
                                                  want_eq=True)
+        if code == "ppdu":
+            dec = engine.decode_ppdu(rx, csi=engine.stream_csi(rec if nb > 1 else rec[0], rx))
+            idx = engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])["scores"][:, 0].long()
+            matched = idx >= 0
+            meta, got = dec["d_meta"][idx.clamp(min=0)], dec["d_psdu"][idx.clamp(min=0)]
+            header_ok = matched & ((meta[:, 0] & abi.PPDU_BAD_HEADER) == 0) & (meta[:, 1] == sent_rate) & (meta[:, 2] == sent_len)
+            fcs_ok = matched & (meta[:, 0] == 0)
+            err = popcount[(got ^ sent).contiguous().view(torch.uint8).long()].sum(dim=1)
+            cols = torch.stack([matched, header_ok, fcs_ok, fcs_ok & (err > 0)], dim=1).long()
+            cols = torch.cat([cols, torch.where(header_ok, err, torch.zeros_like(err))[:, None]], dim=1)
+            ppdu_totals[q].index_add_(0, sent_rate, cols)
+            if keep_packets:
+                kept.append((meta, got, matched))
+            continue
         got = engine.decode_coded(rx, csi=engine.stream_csi(rec if nb > 1 else rec[0], rx), rate=rate)["d_info"]
         idx = engine.score_packets(w, n_data, rx, pos0=gap, stride=stride, window=window, totals=totals[q])["scores"][:, 0].long()
         matched = idx >= 0
@@ -302,13 +342,51 @@ def link_sweep(engine: Engine, words, n_data: int, gap: int, snr_db, cfo_hz: flo
         err = torch.where(matched, popcount[diff.long()].sum(dim=1), torch.zeros_like(idx))
         info_totals[q] += torch.stack([matched.sum() * kinfo, err.sum(), (err > 0).sum()])
     out = dict(snr_db=snr, totals=totals.cpu().numpy(), power=power, packets=n, samples=n_out)
-    if code:
+    if code == "conv":
         out.update(info_totals=info_totals.cpu().numpy())
+    if code == "ppdu":
+        out.update(ppdu_totals=ppdu_totals.cpu().numpy(), rates=ppdu["rates"], lengths=ppdu["lengths"])
+        if keep_packets:
+            out.update(ppdu_packets=[(m.cpu().numpy(), g.cpu().numpy().view(np.uint32), ok.cpu().numpy()) for m, g, ok in kept])
     return out
+
+
+def _ppdu_plan(words, n_data: int, rate, lengths) -> dict:
+    """link_sweep's packets with code="ppdu", checked on the host: psdu (uint32 [n, 31]), rates (int32 codes), lengths,
+    seeds (1 + i mod 127) and sent (the PSDUs as they go out: the FCS in its place, zeros behind)."""
+    from .stream import ppdu_fill  # noqa: PLC0415
+    psdu = words.cpu().numpy() if hasattr(words, "cpu") else np.asarray(words)
+    if psdu.ndim != 2 or psdu.shape[1] != abi.PPDU_PSDU_WORDS or psdu.dtype not in (np.uint32, np.int32):
+        raise ValueError(f"code='ppdu' takes PSDU words uint32 [n, {abi.PPDU_PSDU_WORDS}], got {psdu.dtype} {psdu.shape}")
+    psdu = np.ascontiguousarray(psdu).view(np.uint32)
+    n = len(psdu)
+    if not abi.PPDU_MIN_SYMBOLS <= n_data <= abi.LONG_MAX_DATA_SYMBOLS:
+        raise ValueError(f"code='ppdu' needs n_data in [{abi.PPDU_MIN_SYMBOLS}, {abi.LONG_MAX_DATA_SYMBOLS}], got {n_data!r}")
+    if isinstance(rate, str) and rate == "mixed":
+        rates = np.arange(n, dtype=np.int32) % 3
+    elif isinstance(rate, str) or rate is None:
+        rates = np.full(n, abi.rate_code(rate), np.int32)
+    else:
+        rates = np.array([abi.rate_code(r) for r in rate], np.int32)
+        if len(rates) != n:
+            raise ValueError(f"rate must be one rate, 'mixed' or {n} rates, got {len(rates)}")
+    caps = np.array([abi.ppdu_cap(n_data, r) for r in abi.RATE], np.int32)[rates]
+    ln = caps if lengths is None else np.asarray(lengths).reshape(-1).astype(np.int32)
+    if len(ln) != n:
+        raise ValueError(f"lengths must hold {n} values, got {len(ln)}")
+    bad = (ln < abi.PPDU_MIN_LENGTH) | (ln > caps)
+    if bad.any():
+        k = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"packet {k}: LENGTH must be in [{abi.PPDU_MIN_LENGTH}, {caps[k]}] for {n_data} symbols at rate "
+                         f"{tuple(abi.RATE)[rates[k]]}, got {ln[k]}")
+    return dict(psdu=psdu, rates=rates, lengths=ln, seeds=(1 + np.arange(n) % 127).astype(np.int32), sent=ppdu_fill(psdu, ln))
 
 
 LINK_COLUMNS = ("snr_db", "transmitted", "matched", "missed", "false_alarms", "packet_err", "bit_err", "bits")
 LINK_CODE_COLUMNS = ("info_bits", "info_bit_err", "info_packet_err")     # --code conv: three trailing columns
+# --code ppdu: ppdu_totals' five counts per rate of the sent packet
+LINK_PPDU_COLUMNS = tuple(f"{name}_{r}" for r in ("1of2", "2of3", "3of4")
+                          for name in ("matched", "header_ok", "fcs_ok", "false_accept", "psdu_bit_err"))
 
 
 def parse_snr_grid(text: str) -> np.ndarray:
@@ -328,7 +406,7 @@ def link_main(argv=None) -> int:
     import csv  # noqa: PLC0415
     from .channel import NOISE_KINDS, parse_pdp, parse_taps  # noqa: PLC0415
     from .fileio import write_float_array_to_file  # noqa: PLC0415
-    from .stream import pack_coded_messages, pack_messages  # noqa: PLC0415
+    from .stream import pack_coded_messages, pack_messages, pack_ppdu_messages  # noqa: PLC0415
     ap = argparse.ArgumentParser(prog="ofdm_pkg.py link", description=link_main.__doc__)
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--packets", type=int, help="packets of random payload bits (drawn from --seed)")
@@ -356,18 +434,23 @@ def link_main(argv=None) -> int:
     ap.add_argument("--branches", type=int, default=1,
                     help=f"receive antennas, 1 to {abi.DIVERSITY_MAX_BRANCHES}: independently faded and independently noisy "
                          "recordings of the same packets, combined in the receiver (more than 1 needs --detector conjugate)")
-    ap.add_argument("--code", choices=["conv"], default=None,
+    ap.add_argument("--code", choices=["conv", "ppdu"], default=None,
                     help="conv: the packets carry 48 D - 6 information bits through 802.11a's K = 7 rate-1/2 code; the receiver's "
-                         "equalised subcarriers go through a soft Viterbi decoder weighted with the channel's gains")
-    ap.add_argument("--rate", choices=tuple(abi.RATE), default="1/2",
+                         "equalised subcarriers go through a soft Viterbi decoder weighted with the channel's gains.  "
+                         "ppdu: self-describing packets -- a header symbol names rate and length, the data is scrambled and "
+                         "carries a CRC-32, and the receiver reports a packet error rate without knowing what was sent "
+                         "(--n-data then counts the header's symbol, default 3)")
+    ap.add_argument("--rate", choices=tuple(abi.RATE) + ("mixed",), default="1/2",
                     help="with --code conv: the code's rate; 2/3 and 3/4 are 802.11a's punctured rates, 64 D - 6 and 72 D - 6 "
-                         "information bits per packet")
+                         "information bits per packet.  With --code ppdu also mixed: packet i at rate i mod 3 of the three")
     ap.add_argument("--out", default="data")
     a = ap.parse_args(argv)
     if not 0.0 < a.threshold < 1.0:
         raise SystemExit("--threshold must be inside (0, 1)")
     if a.rate != "1/2" and not a.code:
         raise SystemExit(f"--rate {a.rate} needs --code conv")
+    if a.rate == "mixed" and a.code != "ppdu":
+        raise SystemExit("--rate mixed needs --code ppdu")
     if not 1 <= a.branches <= abi.DIVERSITY_MAX_BRANCHES:
         raise SystemExit(f"--branches must be in [1, {abi.DIVERSITY_MAX_BRANCHES}]")
     if a.branches > 1 and a.detector != "conjugate":
@@ -380,7 +463,22 @@ def link_main(argv=None) -> int:
         texts = [ln for ln in Path(a.messages).read_text(encoding="latin-1").splitlines() if ln]
         if not texts:
             raise SystemExit(f"{a.messages}: no lines")
-        words, d = pack_coded_messages(texts, a.n_data, a.rate) if a.code else pack_messages(texts, a.n_data)
+        if a.code == "ppdu":
+            rates = [tuple(abi.RATE)[i % 3] for i in range(len(texts))] if a.rate == "mixed" else [a.rate] * len(texts)
+            try:
+                words, lengths, d = pack_ppdu_messages(texts, a.n_data, rates)
+            except ValueError as e:
+                raise SystemExit(str(e)) from None
+        else:
+            words, d = pack_coded_messages(texts, a.n_data, a.rate) if a.code else pack_messages(texts, a.n_data)
+    elif a.code == "ppdu":
+        if a.packets < 0:
+            raise SystemExit("--packets must not be negative")
+        d = 3 if a.n_data is None else a.n_data
+        if not abi.PPDU_MIN_SYMBOLS <= d <= abi.LONG_MAX_DATA_SYMBOLS:
+            raise SystemExit(f"--n-data must be in [{abi.PPDU_MIN_SYMBOLS}, {abi.LONG_MAX_DATA_SYMBOLS}] with --code ppdu")
+        words = np.random.default_rng(a.seed).integers(0, 1 << 32, (a.packets, abi.PPDU_PSDU_WORDS), dtype=np.uint64).astype(np.uint32)
+        lengths = None
     else:
         if a.packets < 0:
             raise SystemExit("--packets must not be negative")
@@ -395,7 +493,8 @@ def link_main(argv=None) -> int:
     with Engine(0) as eng:
         res = link_sweep(eng, words, d, a.gap, snr, cfo_hz=a.cfo_hz, taps=None if a.taps is None else parse_taps(a.taps),
                          noise=a.noise, seed=a.seed, fading=fading, detector=a.detector, threshold=a.threshold,
-                         timing=a.timing, tracking=a.tracking, branches=a.branches, code=a.code, rate=a.rate)
+                         timing=a.timing, tracking=a.tracking, branches=a.branches, code=a.code, rate=a.rate,
+                         **(dict(lengths=lengths, keep_packets=bool(a.messages)) if a.code == "ppdu" else {}))
     wall = time.perf_counter() - t0
     t = res["totals"]
     it = res.get("info_totals")
@@ -405,7 +504,8 @@ def link_main(argv=None) -> int:
     write_float_array_to_file(ber if it is None else it[:, 1] / np.maximum(it[:, 0], 1), out / "Output_BER.txt")
     with open(out / "link.csv", "w", newline="") as f:
         wr = csv.writer(f)
-        wr.writerow(LINK_COLUMNS if it is None else LINK_COLUMNS + LINK_CODE_COLUMNS)
+        pt = res.get("ppdu_totals")
+        wr.writerow(LINK_COLUMNS + (() if it is None else LINK_CODE_COLUMNS) + (() if pt is None else LINK_PPDU_COLUMNS))
         for q, (s, r) in enumerate(zip(snr, t)):
             tx, matched, received = int(r[abi.S_TRANSMITTED]), int(r[abi.S_MATCHED]), int(r[abi.S_RECEIVED])
             row = [f"{s:g}", tx, matched, tx - matched, received - matched, int(r[abi.S_PACKET_ERR]),
@@ -415,8 +515,20 @@ def link_main(argv=None) -> int:
             if it is not None:
                 row += [int(v) for v in it[q]]
                 line += f"   information BER = {it[q, 1] / max(int(it[q, 0]), 1):.3e}"
+            if pt is not None:
+                row += [int(v) for v in pt[q].ravel()]
+                for name, c in zip(abi.RATE, pt[q]):
+                    # blind: what the receiver sees (header invalid or FCS failed); true: the PSDU is not the sent one
+                    m, blind = max(int(c[0]), 1), int(c[0] - c[2])
+                    line += (f"\n    rate {name}: matched {c[0]}, header right {c[1]}, FCS passed {c[2]}, blind PER {blind / m:.3e}, "
+                             f"true PER {(blind + int(c[3])) / m:.3e}, false accepts {c[3]}")
             wr.writerow(row)
             print(line, file=sys.stderr)
+            if pt is not None and a.messages:
+                meta, psdu, ok = res["ppdu_packets"][q]
+                for k in np.nonzero(ok & (meta[:, 0] == 0))[0]:          # only texts whose FCS passed
+                    body = psdu[k].astype(">u4").tobytes()[:int(meta[k, 2]) - 4]
+                    print(f"SNR = {s:g} dB  packet {k}: {body.decode('latin-1')}")
     print(f"{res['packets']} packets of {d} data symbols, {res['samples']} samples, {len(snr)} SNR points in {wall:.2f} s "
           f"-> {out / 'link.csv'}", file=sys.stderr)
     return 0
